@@ -248,14 +248,44 @@ def log(*a):
     print('[bench]', *a, file=sys.stderr, flush=True)
 
 
+# --dump-outputs: at most this many bytes in all; an array is written whole up to `limit` elements, above that as the
+# elements at a fixed, seeded set of positions of its flattened form (the same positions in every run)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(t, limit):
+    t = t.detach()
+    if t.numel() <= limit:
+        return t
+    idx = np.sort(np.random.default_rng(0).choice(t.numel(), limit, replace=False))
+    return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """write {name: tensor} as out_dir/<name>.npy: float64 stays float64, every other dtype becomes float32"""
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.double().numpy() if t.dtype == torch.float64 else t.float().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError('--dump-outputs: {} bytes exceed the {} byte budget'.format(total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    log('dumped {} arrays ({:.1f} MB) to {}'.format(len(host), total / 1e6, out_dir))
+
+
 def infer_main(args, model, x, world, rank, dev):
     """config 2: eval-mode forward + decode of a resident batch (replicas only: no collective)"""
     from utils.heatmap_decoding import get_final_preds
     model.eval()
 
-    def step():
+    def step(keep=None):
         with torch.no_grad():
             hm, _ = model(x)
+            if keep is not None:
+                keep['heatmaps'] = hm
             return get_final_preds(hm, use_softmax=False)
     for _ in range(args.warmup):
         step()
@@ -264,9 +294,10 @@ def infer_main(args, model, x, world, rank, dev):
         import torch.distributed as dist
         dist.barrier()
     torch.cuda.synchronize()
+    keep = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        preds = step()
+    for i in range(args.steps):
+        preds = step(keep if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -276,6 +307,8 @@ def infer_main(args, model, x, world, rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'preds': preds, 'heatmaps': dump_sample(keep['heatmaps'], 1 << 23)})
     if rank == 0:
         value = world * args.batch * args.steps / dt
         peak = PEAK_TFLOPS[args.dtype]
@@ -313,10 +346,14 @@ def dcn_main(args, world, rank, dev):
         go = torch.randn(B, 21, 64, 64, device=dev, generator=g)
         cases.append((dd, x, off, w, go))
 
-    def step():
+    def step(keep=None):
         for dd, x, off, w, go in cases:
             x.grad = off.grad = w.grad = None
-            DeformConvFunction.apply(x, off, w, None, 1, dd, dd, 1, 21, 64).backward(go)
+            y = DeformConvFunction.apply(x, off, w, None, 1, dd, dd, 1, 21, 64)
+            y.backward(go)
+            if keep is not None:
+                keep[dd] = y.detach()
+            del y
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -324,9 +361,10 @@ def dcn_main(args, world, rank, dev):
         import torch.distributed as dist
         dist.barrier()
     torch.cuda.synchronize()
+    keep = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -336,6 +374,15 @@ def dcn_main(args, world, rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        outs = {}
+        for dd, x, off, w, go in cases:
+            outs.update({'d{}_output'.format(dd): dump_sample(keep[dd], 1 << 19),
+                         'd{}_grad_input'.format(dd): dump_sample(x.grad, 1 << 19),
+                         'd{}_grad_offset'.format(dd): dump_sample(off.grad, 1 << 19),
+                         'd{}_grad_weight'.format(dd): w.grad})
+        dump_outputs(args.dump_outputs, outs)
+        del outs, keep
     # per-pass kernel times on the launch stream (events around the C-ABI calls themselves - autograd's graph walk and
     # its accumulation of the 396 MB offset gradient into .grad stay out of the kernel figure), one dilation
     from hipnet import _capi as C
@@ -411,7 +458,25 @@ def main():
                          'CPU baseline at 1 thread and at batch 64')
     ap.add_argument('--no-selfcheck', action='store_true',
                     help='skip the (untimed) loss comparison with the fp32 device path and the data-parallel-mode A/B')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; '
+                         'float32, float64 arrays as float64; at most 64 MB: large arrays as a fixed, seeded sample of '
+                         'their elements). The inputs are the same in every run. Training mode: the steps sum BatchNorm '
+                         'batch statistics in a fixed order (HRNET_DETERMINISTIC=1: per-BatchNorm finalize launches '
+                         'instead of the default float-atomic sums, so ms_per_step is that of the slower ordered form), '
+                         'and the last timed step starts from the seeded initial weights, BatchNorm buffers and '
+                         'optimiser state (reset outside the clock; that step starts on an idle queue)')
     args = ap.parse_args()
+
+    # --dump-outputs, training mode: BatchNorm batch sums in a fixed order (HRNET_DETERMINISTIC=1; weight gradients still
+    # by float atomics, HRNET_WGRAD_ATOMIC=1), read when the step's plans are recorded. The default sums by float
+    # atomics, and the chaotic forward pass turns their order into heat maps that differ from run to run by far more
+    # than rounding; the ordered form repeats bit for bit and costs about 0.4 ms/step. Restored after the timed region.
+    saved_env = None
+    if args.dump_outputs and args.mode == 'train':
+        saved_env = {k: os.environ.get(k) for k in ('HRNET_DETERMINISTIC', 'HRNET_WGRAD_ATOMIC')}
+        os.environ['HRNET_DETERMINISTIC'] = '1'
+        os.environ.setdefault('HRNET_WGRAD_ATOMIC', '1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -453,11 +518,16 @@ def main():
     sync = None
     if world > 1:
         sync = GradSync(model, optimizer=opt)
+    # --dump-outputs: the seeded state before any step (weights, BatchNorm buffers, optimiser moments), on the device
+    init_state = None
+    if args.dump_outputs and args.mode == 'train':
+        init_state = ({k: v.detach().clone() for k, v in model.state_dict().items()},
+                      {k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state_dict().items()})
 
     if args.mode == 'infer':
         return infer_main(args, model, x, world, rank, dev)
 
-    def step():
+    def step(keep=None):
         opt.zero_grad()
         hm, _ = model(x)
         loss = criterion(hm, gt)
@@ -465,6 +535,8 @@ def main():
         if sync is not None:
             sync.finish()
         opt.step()
+        if keep is not None:
+            keep['heatmaps'] = hm.detach()
         return loss
 
     if args.pose2d_loss:
@@ -479,7 +551,7 @@ def main():
         ret = {'imgs': x, 'heatmaps': gt, 'pose2d': torch.from_numpy(b['pose2d']).to(dev),
                'visibility': torch.from_numpy(b['visibility']).to(dev)}
 
-        def step():      # noqa: F811
+        def step(keep=None):      # noqa: F811  (the heat maps stay inside _forward_and_losses: not dumped)
             _imgs, loss_dict = _forward_and_losses(cfg, ret, model, recorder, dev)
             opt.zero_grad()
             loss_dict['total_loss'].backward()
@@ -510,21 +582,53 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    keep = {} if args.dump_outputs else None
+    paused = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        if keep is not None and i == args.steps - 1:
+            # --dump-outputs: the dumped step starts from the seeded initial state, so that its inputs are the same in
+            # every run (the steps before it sum by float atomics, and training amplifies that rounding from step to
+            # step: the loss of the default run differs by several per cent after 25 steps). The reset is not timed.
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            model.load_state_dict(init_state[0])
+            opt.load_state_dict(init_state[1])
+            torch.cuda.synchronize()
+            paused += time.perf_counter() - tp
+        loss = step(keep if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - paused
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
+    if saved_env is not None:
+        for k, v in saved_env.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     if prio_ctx is not None:
         prio_ctx.__exit__(None, None, None)
+    if rank == 0 and args.dump_outputs:
+        # the step's loss and heat maps, and the state it leaves behind: parameters after the Adam update, their
+        # gradients, BatchNorm running statistics (parameters in module order, not the engine's flat order)
+        params = list(model.parameters())
+        flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+        outs = {'loss': loss.detach().reshape(1), 'params': dump_sample(flat_p, 1 << 20),
+                'grads': dump_sample(flat_g, 1 << 20),
+                'bn_running_stats': torch.cat([v.reshape(-1) for k, v in model.state_dict().items()
+                                               if k.endswith(('running_mean', 'running_var'))])}
+        if 'heatmaps' in keep:
+            outs['heatmaps'] = dump_sample(keep['heatmaps'], 1 << 23)
+        dump_outputs(args.dump_outputs, outs)
+        del params, flat_p, flat_g, outs, keep
 
     roof = None
     extra_out = {}
