@@ -8,14 +8,25 @@ import numpy as np
 import torch
 
 
-def load_checkpoint_state(model, path, map_location='cpu'):
+def load_checkpoint_state(model, path, map_location='cpu', strict=True, info=None):
     """torch.load(path) -> optional 'state_dict' entry -> strip the `module.` prefix DataParallel / DDP
-    checkpoints carry (tools/evaluate_2D.py:127-129, tools/train.py:166-168) -> load_state_dict(strict=True)."""
-    sd = torch.load(path, map_location=map_location)
+    checkpoints carry (tools/evaluate_2D.py:127-129, tools/train.py:166-168) -> load_state_dict(strict).
+
+    strict=False is tools/inference.py's load (reference tools/inference.py:83,89): keys missing from the
+    checkpoint keep the model's values and extra keys are ignored, but a checkpoint that matches none of the
+    model's keys is refused. A dict passed as `info` receives 'missing', 'unexpected' (key lists) and 'epoch'
+    (the checkpoint's 'epoch' entry, or None)."""
+    ckpt = torch.load(path, map_location=map_location)
+    sd = ckpt
     if isinstance(sd, dict) and 'state_dict' in sd and not torch.is_tensor(sd['state_dict']):
         sd = sd['state_dict']
     sd = {(k[7:] if k.startswith('module.') else k): v for k, v in sd.items()}
-    model.load_state_dict(sd, strict=True)
+    if not strict and not set(sd) & set(model.state_dict()):
+        raise ValueError('{}: none of its {} keys is a key of {}'.format(path, len(sd), type(model).__name__))
+    res = model.load_state_dict(sd, strict=strict)
+    if info is not None:
+        info['missing'], info['unexpected'] = list(res.missing_keys), list(res.unexpected_keys)
+        info['epoch'] = ckpt.get('epoch') if isinstance(ckpt, dict) and not torch.is_tensor(ckpt.get('epoch')) else None
     return model
 
 

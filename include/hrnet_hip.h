@@ -533,6 +533,21 @@ int hrnet_normalize_u8(const unsigned char* img_nhwc, float* out_nchw, int N, in
                        const float* mean3, const float* std3, hr_stream_t stream);
 
 /*
+ * Input step of tools/inference.py (reference tools/inference.py:117-121: cv2.resize to IMAGE_SIZE, then
+ * ToTensor + Normalize): a ragged batch of u8 HWC images in ONE device buffer of src_bytes bytes ->
+ * out_nchw [n,3,Ho,Wo] f32. slots is a DEVICE table int64 [n][4] = {byte offset, H, W, row pitch (bytes)};
+ * several rows may name the same bytes (PoseAggr frame windows). Resize: cv2 INTER_LINEAR geometry
+ * (sx = (x+0.5)*W/Wo - 0.5, negative -> 0 with weight 0, x1 = min(x0+1, W-1); no antialiasing), the
+ * blend in f32, rounded half to even and clamped to a u8 code, then (u/255 - mean[c]) / std[c] as
+ * hrnet_normalize_u8 (bit-identical to it at Ho == H, Wo == W). Channel c is read from source channel
+ * bgr ? 2-c : c. A row whose extent offset + (H-1)*pitch + 3*W exceeds src_bytes, or with H, W < 1 or
+ * pitch < 3*W, is not read: its output plane is NaN. mean3/std3 are HOST arrays of 3 floats.
+ */
+int hrnet_resize_normalize_u8(const unsigned char* src, int64_t src_bytes, const int64_t* slots, int n,
+                              float* out_nchw, int Ho, int Wo, const float* mean3, const float* std3,
+                              int bgr, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
