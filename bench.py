@@ -10,6 +10,13 @@ One JSON line on rank 0 (contract in the task statement). A "step" = one pass of
 one synthetic RHD-shaped batch already resident in HBM: model forward, HeatmapLoss, backward,
 gradient all-reduce (N > 1, RCCL, overlapped with backward), fused Adam update.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; its figures beside the headline
+are those computed from the timed steps alone (cpu_baseline is null; roofline is null but at --mode infer). --full adds
+everything that takes runs of its own, after the timed region: the per-kernel roofline pass, the self-check against the
+fp32 device path (exit code 3 on failure), the data-parallel-mode step, the fp32 and WITH_POSE2D_LOSS steps and the CPU
+baselines (--no-roofline, --no-selfcheck, --no-extras and --no-cpu-baseline leave out parts of it); at --mode dcn, the
+per-pass kernel timings.
+
 roofline      per-kernel HIP-event timing of one instrumented step (after the timed region); the
               dominant MFMA kernel instantiation's algorithmic FLOP/launch over its mean launch time,
               against the dense MFMA peak of the dtype (MI355X_MICROARCH.md: bf16 2.5 PF, f32 157.3 TF).
@@ -328,6 +335,48 @@ def infer_main(args, model, x, world, rank, dev):
         dist.destroy_process_group()
 
 
+def dcn_pass_roofline(case, B, dev):
+    """--mode dcn --full: per-pass kernel times on the launch stream (events around the C-ABI calls themselves -
+    autograd's graph walk and its accumulation of the 396 MB offset gradient into .grad stay out of the kernel figure),
+    one dilation, against the HBM peak"""
+    from hipnet import _capi as C
+    dd, x, off, w, go = case
+    xd, od, wd = x.detach(), off.detach(), w.detach()
+    out = torch.empty(B, 21, 64, 64, device=dev)
+    gx, goff, gw = torch.empty_like(xd), torch.empty_like(od), torch.empty_like(wd)
+    blocks = C.call('hrnet_deform_conv_wgrad_blocks', B, 64, 64)
+    scratch = torch.empty(blocks * 21 * 21 * 9, device=dev)
+
+    def fwd_call():
+        C.call('hrnet_deform_conv_forward', C.ptr(xd), C.ptr(od), C.ptr(wd), None, C.ptr(out), B, 21, 64, 64, 21, 3, 3,
+               1, 1, dd, dd, dd, dd, 1, 21, C.stream_ptr())
+
+    def bwd_call():
+        C.call('hrnet_deform_conv_backward', C.ptr(xd), C.ptr(od), C.ptr(wd), C.ptr(go), C.ptr(gx), C.ptr(goff),
+               C.ptr(gw), None, C.ptr(scratch), B, 21, 64, 64, 21, 3, 3, 1, 1, dd, dd, dd, dd, 1, 21, C.stream_ptr())
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    n = 10
+    fwd_call(); bwd_call()
+    torch.cuda.synchronize()
+    ev[0].record()
+    for _ in range(n):
+        fwd_call()
+    ev[1].record()
+    for _ in range(n):
+        bwd_call()
+    ev[2].record()
+    torch.cuda.synchronize()
+    tf, tb = ev[0].elapsed_time(ev[1]) / n, ev[1].elapsed_time(ev[2]) / n
+    by_f = (off.numel() + x.numel() + out.numel()) * 4
+    by_b = (2 * off.numel() + 2 * x.numel() + out.numel()) * 4          # offsets read + offset gradient written
+    ach = by_b / (tb * 1e-3) / 1e9
+    return {'bound': 'hbm', 'achieved': round(ach, 1), 'peak': 8000.0, 'unit': 'GB/s',
+            'frac': round(ach / 8000.0, 4), 'traffic': None, 'kernel': 'dcn_bwd_fused_kernel (backward, dilation 12)',
+            'avg_launch_us': round(tb * 1e3, 1), 'algorithmic_bytes_per_launch': by_b,
+            'forward': {'achieved': round(by_f / (tf * 1e-3) / 1e9, 1), 'avg_launch_us': round(tf * 1e3, 1),
+                        'algorithmic_bytes_per_launch': by_f}}
+
+
 def dcn_main(args, world, rank, dev):
     """config 5 (BASELINE.json): the deformable-convolution branch of pose_hrnet_PoseAggr at its geometry
     (reference lib/models/pose_hrnet_PoseAggr.py:508-516,615-628): input (B,21,64,64), offsets (B,378,64,64),
@@ -383,41 +432,11 @@ def dcn_main(args, world, rank, dev):
                          'd{}_grad_weight'.format(dd): w.grad})
         dump_outputs(args.dump_outputs, outs)
         del outs, keep
-    # per-pass kernel times on the launch stream (events around the C-ABI calls themselves - autograd's graph walk and
-    # its accumulation of the 396 MB offset gradient into .grad stay out of the kernel figure), one dilation
-    from hipnet import _capi as C
-    dd, x, off, w, go = cases[2]
-    xd, od, wd = x.detach(), off.detach(), w.detach()
-    out = torch.empty(B, 21, 64, 64, device=dev)
-    gx, goff, gw = torch.empty_like(xd), torch.empty_like(od), torch.empty_like(wd)
-    blocks = C.call('hrnet_deform_conv_wgrad_blocks', B, 64, 64)
-    scratch = torch.empty(blocks * 21 * 21 * 9, device=dev)
-
-    def fwd_call():
-        C.call('hrnet_deform_conv_forward', C.ptr(xd), C.ptr(od), C.ptr(wd), None, C.ptr(out), B, 21, 64, 64, 21, 3, 3,
-               1, 1, dd, dd, dd, dd, 1, 21, C.stream_ptr())
-
-    def bwd_call():
-        C.call('hrnet_deform_conv_backward', C.ptr(xd), C.ptr(od), C.ptr(wd), C.ptr(go), C.ptr(gx), C.ptr(goff),
-               C.ptr(gw), None, C.ptr(scratch), B, 21, 64, 64, 21, 3, 3, 1, 1, dd, dd, dd, dd, 1, 21, C.stream_ptr())
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    n = 10
-    fwd_call(); bwd_call()
-    torch.cuda.synchronize()
-    ev[0].record()
-    for _ in range(n):
-        fwd_call()
-    ev[1].record()
-    for _ in range(n):
-        bwd_call()
-    ev[2].record()
-    torch.cuda.synchronize()
-    tf, tb = ev[0].elapsed_time(ev[1]) / n, ev[1].elapsed_time(ev[2]) / n
-    by_f = (off.numel() + x.numel() + out.numel()) * 4
-    by_b = (2 * off.numel() + 2 * x.numel() + out.numel()) * 4          # offsets read + offset gradient written
+    roof = None
+    if not args.no_roofline:
+        roof = dcn_pass_roofline(cases[2], B, dev)
     if rank == 0:
         value = world * B * args.steps / dt
-        ach = by_b / (tb * 1e-3) / 1e9
         print(json.dumps({
             'metric': 'images/sec fwd+bwd DCNv1 branch of pose_hrnet_PoseAggr (5 dilations) 21ch 64x64 bs={}/GPU'.format(B),
             'value': round(value, 2), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -426,17 +445,12 @@ def dcn_main(args, world, rank, dev):
             'config': {'workload': 'deformable conv v1 forward+backward, input (B,21,64,64), offsets (B,378,64,64), 3x3, '
                                    'dilations 3/6/12/18/24, 21 deformable groups, batch {}/GPU'.format(B),
                        'global_batch': world * B, 'parallelism': 'replicas{}'.format(world)},
-            'roofline': {'bound': 'hbm', 'achieved': round(ach, 1), 'peak': 8000.0, 'unit': 'GB/s',
-                         'frac': round(ach / 8000.0, 4), 'traffic': None, 'kernel': 'dcn_bwd_fused_kernel (backward, dilation 12)',
-                         'avg_launch_us': round(tb * 1e3, 1), 'algorithmic_bytes_per_launch': by_b,
-                         'forward': {'achieved': round(by_f / (tf * 1e-3) / 1e9, 1), 'avg_launch_us': round(tf * 1e3, 1),
-                                     'algorithmic_bytes_per_launch': by_f}},
-            'cpu_baseline': None}))
+            'roofline': roof, 'cpu_baseline': None}))
     if world > 1:
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -448,16 +462,21 @@ def main():
     ap.add_argument('--mode', default='train', choices=['train', 'infer', 'dcn'],
                     help='train = the headline step (default); infer = BASELINE.json config 2: eval forward + '
                          'arg-max decode (use with --dtype fp32)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also measure and check what takes runs of its own: per-kernel '
+                         'roofline pass, self-check against the fp32 device path, data-parallel-mode, fp32 and '
+                         'WITH_POSE2D_LOSS steps, CPU baselines (a plain run prints the headline line alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the per-kernel roofline pass')
     ap.add_argument('--pose2d-loss', action='store_true',
                     help='the WITH_POSE2D_LOSS form of the step (SURVEY 8d): decode + JointsMSELoss added through '
                          'core.function.AverageMeter.computeLosses, with its three .item() syncs per step as the reference has')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the extra (untimed, child-process) figures: fp32 training step, WITH_POSE2D_LOSS step, '
-                         'CPU baseline at 1 thread and at batch 64')
+                    help='with --full: skip the extra (untimed, child-process) figures: fp32 training step, '
+                         'WITH_POSE2D_LOSS step, CPU baseline at 1 thread and at batch 64')
     ap.add_argument('--no-selfcheck', action='store_true',
-                    help='skip the (untimed) loss comparison with the fp32 device path and the data-parallel-mode A/B')
+                    help='with --full: skip the (untimed) loss comparison with the fp32 device path, the '
+                         'data-parallel-mode A/B and the extra figures')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; '
                          'float32, float64 arrays as float64; at most 64 MB: large arrays as a fixed, seeded sample of '
@@ -466,7 +485,15 @@ def main():
                          'instead of the default float-atomic sums, so ms_per_step is that of the slower ordered form), '
                          'and the last timed step starts from the seeded initial weights, BatchNorm buffers and '
                          'optimiser state (reset outside the clock; that step starts on an idle queue)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: nothing after the timed region but --dump-outputs and the result line
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = args.no_selfcheck = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # --dump-outputs, training mode: BatchNorm batch sums in a fixed order (HRNET_DETERMINISTIC=1; weight gradients still
     # by float atomics, HRNET_WGRAD_ATOMIC=1), read when the step's plans are recorded. The default sums by float
@@ -633,7 +660,7 @@ def main():
     roof = None
     extra_out = {}
     if rank == 0:
-        log('timed region {:.3f} s; instrumented per-kernel pass'.format(dt))
+        log('timed region {:.3f} s{}'.format(dt, '' if args.no_roofline else '; instrumented per-kernel pass'))
     if rank == 0 and not args.no_roofline:
         stats, kinds = instrumented_step(model, x, gt, criterion)
         peak = PEAK_TFLOPS[args.dtype]
@@ -740,7 +767,7 @@ def main():
             import subprocess
             env = dict(os.environ, HRNET_DP_PLAN='1')
             cmd = [sys.executable, os.path.abspath(__file__), '--steps', '10', '--warmup', '5', '--batch', str(args.batch),
-                   '--dtype', args.dtype, '--arch', args.arch, '--no-cpu-baseline', '--no-roofline', '--no-selfcheck']
+                   '--dtype', args.dtype, '--arch', args.arch]
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
             line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
             extra_out['dp_mode_ms_per_step_1gpu'] = json.loads(line)['ms_per_step']
@@ -750,10 +777,11 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_selfcheck and not args.no_extras and args.arch == 'w32':
         # (3) figures SURVEY 8d asks for beside the headline, each in a child process of its own (bounded: ~15 s each):
-        # the step in the reference's own arithmetic (fp32), and the WITH_POSE2D_LOSS form of the headline step
+        # the step in the reference's own arithmetic (fp32), and the WITH_POSE2D_LOSS form of the headline step (plain
+        # runs, like the data-parallel-mode one above)
         import subprocess
         base = [sys.executable, os.path.abspath(__file__), '--steps', '8', '--warmup', '3', '--batch', str(args.batch),
-                '--arch', args.arch, '--no-cpu-baseline', '--no-roofline', '--no-selfcheck']
+                '--arch', args.arch]
         for key, extra_args in (('fp32_train_ms_per_step', ['--dtype', 'fp32']),
                                 ('with_pose2d_loss_ms_per_step', ['--dtype', args.dtype, '--pose2d-loss'])):
             try:

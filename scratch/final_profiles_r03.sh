@@ -4,14 +4,14 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final_r03
 mkdir -p $O
-python bench.py > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/r03_bench_final.json
+python bench.py --full > $O/bench_default.log 2>&1 && tail -1 $O/bench_default.log > $O/r03_bench_final.json
 echo "default done: $(python -c "import json;d=json.load(open('$O/r03_bench_final.json'));print(d['ms_per_step'], d['value'], d.get('selfcheck'), d.get('dp_mode_ms_per_step_1gpu'))")"
 if [ "$1" != "quick" ]; then
 python bench.py --mode infer --dtype fp32 --no-cpu-baseline --no-roofline > $O/c2_fp32.log 2>&1; tail -1 $O/c2_fp32.log > $O/c2_fp32.json
 python bench.py --mode infer --dtype bf16 --no-cpu-baseline --no-roofline > $O/c2_bf16.log 2>&1; tail -1 $O/c2_bf16.log > $O/c2_bf16.json
 python bench.py --dtype fp32 --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-selfcheck > $O/c3_fp32.log 2>&1; tail -1 $O/c3_fp32.log > $O/c3_fp32.json
-python bench.py --arch w48 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline --no-selfcheck > $O/c4_w48.log 2>&1; tail -1 $O/c4_w48.log > $O/c4_w48.json
-python bench.py --mode dcn --no-cpu-baseline > $O/c5_dcn.log 2>&1; tail -1 $O/c5_dcn.log > $O/c5_dcn.json
+python bench.py --full --arch w48 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline --no-selfcheck > $O/c4_w48.log 2>&1; tail -1 $O/c4_w48.log > $O/c4_w48.json
+python bench.py --full --mode dcn --no-cpu-baseline > $O/c5_dcn.log 2>&1; tail -1 $O/c5_dcn.log > $O/c5_dcn.json
 echo "configs done"
 fi
 rm -rf gpurun_out/rp_r03
