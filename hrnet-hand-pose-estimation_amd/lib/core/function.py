@@ -6,6 +6,10 @@ Same call signatures, loss-dict keys, log line format and tensorboard scalar nam
 generic 2-D dataset branch (HandGraph_kpt / RHD_kpt / FreiHand_kpt / MHP_kpt ...) exists here -
 the multi-view / temporal / CPM branches belong to other model families.
 
+`validate` also accepts 'RHD' (the evaluation-set reader, dataset/rhd.py; tools/train.py serves it with heat
+maps). The reference's validate skips that name (function.py:800), so validating on the shipped RHD yaml's
+TEST_DATASET did nothing there; here it computes the validation losses.
+
 `debug`: the reference hard-codes a module-level `debug = True` that stops every epoch after 5
 iterations (function.py:22,193,812). Here it defaults to False; set `core.function.debug = True`
 to reproduce that behaviour.
@@ -19,6 +23,7 @@ from utils.heatmap_decoding import get_final_preds
 debug = False
 
 GENERIC_DATASETS = ('HandGraph_kpt', 'RHD_kpt', 'FreiHand_kpt', 'MHP_kpt', 'MHP_CPM_kpt', 'MHP_seq', 'synthetic_kpt')
+VALID_DATASETS = GENERIC_DATASETS + ('RHD',)
 
 _LOSS_NAMES = (('heatmap_loss', 'WITH_HEATMAP_LOSS', 'HeatmapLoss', 'heatmap_loss'),
                ('pose2d_loss', 'WITH_POSE2D_LOSS', 'Pose2DLoss', 'pose2d_loss'))
@@ -192,7 +197,7 @@ def validate(config, args, master, val_loader_dict, model, criterion, output_dir
     model.eval()
     for dataset_name, val_loader in val_loader_dict.items():
         logger.info('Validating on {} dataset [Batch size: {}]\n'.format(dataset_name, val_loader.batch_size))
-        if dataset_name not in GENERIC_DATASETS:
+        if dataset_name not in VALID_DATASETS:
             raise NotImplementedError('dataset branch {} is outside the HRNet 2-D hot path'.format(dataset_name))
         with torch.no_grad():
             for i, ret in enumerate(val_loader):

@@ -1,10 +1,23 @@
-"""Loader on the input side of the hot path. No dataset ships with the repository, so the loader is
-synthetic and RHD-shaped: it yields the sample dict of the reference's RHD key-point dataset
-(lib/dataset/RHDDatasetKeypoints.py:126-134; batch = IMAGES_PER_GPU * number of GPUs of this
-process, lib/dataset/build.py:66-97) from the portable generator in hipnet/synth.py."""
+"""Loaders on the input side of the hot path (reference lib/dataset/build.py:31-97).
+
+make_dataloader builds the named datasets (DATASET.DATASET with TRAIN_SET for training, TEST_DATASET with TEST_SET
+otherwise) when they are RHD readers (dataset/rhd.py: RHD_kpt, RHD) and <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle
+exists. Otherwise it logs one warning naming what is missing and returns the synthetic RHD-shaped loader: it yields
+the sample dict of the reference's RHD key-point dataset (lib/dataset/RHDDatasetKeypoints.py:126-134) from the
+portable generator in hipnet/synth.py, so the tests and bench.py run without a dataset.
+
+Real loaders: training shuffles with DistributedSampler semantics (this rank's share when `distributed` and
+world > 1; set_epoch reshuffles), validation / evaluation keep order and every sample. The batch is
+IMAGES_PER_GPU (one process per GPU). `max_batches` caps a real epoch; `num_batches` is the synthetic length."""
+import logging
+import os
+
 import torch
 
+from dataset import rhd
 from hipnet import synth
+
+logger = logging.getLogger(__name__)
 
 
 class SyntheticRHD(torch.utils.data.Dataset):
@@ -46,7 +59,20 @@ class SyntheticLoader(object):
             yield self.dataset.batch(i * self.world + self.rank, self.batch_size)
 
 
-def make_dataloader(cfg, is_train=True, distributed=False, num_batches=8, rank=0, world=1):
+def make_dataloader(cfg, is_train=True, distributed=False, num_batches=8, rank=0, world=1, max_batches=None,
+                    heatmaps=None):
+    """{dataset name: loader}. heatmaps=None: RHD_kpt batches carry heat maps and RHD batches do not; True / False
+    forces it (tools/train.py validates on RHD with heat maps)."""
+    names = list(cfg.DATASET.DATASET if is_train else cfg.DATASET.TEST_DATASET)
+    subset = cfg.DATASET.TRAIN_SET if is_train else cfg.DATASET.TEST_SET
+    anno = rhd.annotation_path(cfg.DATA_DIR, subset)
+    unknown = [n for n in names if n not in rhd.READERS]
+    if names and not unknown and os.path.exists(anno):
+        return {n: rhd.make_loader(cfg, n, subset, is_train, rank, world, distributed, max_batches, heatmaps)
+                for n in names}
+    why = 'no reader for {}'.format(unknown) if unknown else 'no datasets named' if not names else \
+        '{} not found'.format(anno)
+    logger.warning('%s: using the synthetic RHD-shaped loader', why)
     per_gpu = cfg.TRAIN.IMAGES_PER_GPU if is_train else cfg.TEST.IMAGES_PER_GPU
     ds = SyntheticRHD(cfg, length=per_gpu * num_batches * world, seed=1234 if is_train else 4321)
     return {'synthetic_kpt': SyntheticLoader(ds, per_gpu, num_batches, rank, world)}

@@ -1,6 +1,7 @@
 """Input step of tools/inference.py (reference tools/inference.py:117-121 + :196-213): read whole images, pack a
 ragged batch of them into one staging buffer, and resize + normalise the batch on the device with one HIP launch
-(hrnet_resize_normalize_u8, csrc/preprocess.hip).
+(hrnet_resize_normalize_u8, csrc/preprocess.hip). The RHD reader (dataset/rhd.py) packs the same way and warps its
+crops with affine_warp_normalize (hrnet_affine_warp_normalize_u8).
 
 The reference reads with cv2.imread(IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION), resizes with cv2.resize (INTER_LINEAR)
 to MODEL.IMAGE_SIZE, swaps BGR -> RGB and applies ToTensor + Normalize (its affine step is the identity on an
@@ -107,6 +108,37 @@ def resize_normalize(buffer, table, size, bgr=False, mean=IMAGENET_MEAN, std=IMA
     s = (ctypes.c_float * 3)(*std)
     C.call('hrnet_resize_normalize_u8', buffer.data_ptr(), buffer.numel(), slots.data_ptr(), n, out.data_ptr(), ho, wo,
            m, s, int(bool(bgr)), C.stream_ptr())
+    return out
+
+
+def affine_warp_normalize(buffer, table, inv_mats, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, validate=True):
+    """buffer: uint8 1-D tensor on the HIP device; table: (n, 4) int64 HOST slot table (a crop is a slot pointing into
+    its image, dataset/rhd.py); inv_mats: (n, 2, 3) or (n, 6) HOST inverse matrices, output pixel -> slot pixel;
+    size: (width, height) -> (n, 3, height, width) f32 on the device: warpAffine (INTER_LINEAR, BORDER_CONSTANT 0 outside
+    the slot) + ToTensor + Normalize in one launch of hrnet_affine_warp_normalize_u8 (csrc/preprocess.hip)."""
+    from hipnet import _capi as C
+    if not isinstance(buffer, torch.Tensor) or not buffer.is_cuda or buffer.dtype != torch.uint8 or buffer.dim() != 1:
+        raise RuntimeError('affine_warp_normalize expects a 1-D uint8 tensor on the HIP device (no CPU path)')
+    t = torch.as_tensor(table)
+    m = torch.as_tensor(inv_mats)
+    if t.is_cuda or m.is_cuda:
+        raise ValueError('affine_warp_normalize: pass the slot table and the matrices on the host')
+    t = t.to(torch.int64).contiguous()
+    m = m.to(torch.float32).reshape(-1, 6).contiguous()
+    if validate:
+        validate_table(t, buffer.numel())
+    n = t.shape[0]
+    if m.shape[0] != n:
+        raise ValueError('affine_warp_normalize: {} matrices for {} slots'.format(m.shape[0], n))
+    wo, ho = int(size[0]), int(size[1])
+    dev = buffer.device
+    slots = t.pin_memory().to(dev, non_blocking=True)
+    mats = m.pin_memory().to(dev, non_blocking=True)
+    out = torch.empty((n, 3, ho, wo), dtype=torch.float32, device=dev)
+    cm = (ctypes.c_float * 3)(*mean)
+    cs = (ctypes.c_float * 3)(*std)
+    C.call('hrnet_affine_warp_normalize_u8', buffer.data_ptr(), buffer.numel(), slots.data_ptr(), mats.data_ptr(), n,
+           out.data_ptr(), ho, wo, cm, cs, C.stream_ptr())
     return out
 
 

@@ -133,6 +133,8 @@ _SIGS = {
     'hrnet_normalize_u8': [_c_vp, _c_vp] + [_c_int] * 3 + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_vp],
     'hrnet_resize_normalize_u8': [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_int]
                                  + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_int, _c_vp],
+    'hrnet_affine_warp_normalize_u8': [_c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_int]
+                                      + [ctypes.POINTER(ctypes.c_float)] * 2 + [_c_vp],
     'hrnet_spatial_softmax_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],
     'hrnet_spatial_softmax_bwd': [_c_vp] * 6 + [_c_int] * 2 + [_c_vp],
     'hrnet_im2col_stem': [_c_int, _c_vp, _c_vp] + [_c_int] * 7 + [_c_vp],

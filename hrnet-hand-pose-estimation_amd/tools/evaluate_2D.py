@@ -5,7 +5,10 @@
 cfg -> get_pose_net(is_train=False) -> strict load ('module.' prefix stripped) -> eval loop:
 model(imgs) + get_final_preds -> per-joint end-point error (pixels of the input crop) weighted by
 visibility, PCK for thresholds 1..49 px, fps after 20 warm-up iterations; writes
-mse2d_each_joint.txt and PCK2d.txt (tools/evaluate_2D.py:172-294). Data: synthetic RHD-shaped loader.
+mse2d_each_joint.txt and PCK2d.txt (tools/evaluate_2D.py:172-294). Data: TEST_DATASET / TEST_SET through
+dataset/build.py - the RHD reader (every sample, in order; --num_batches caps it only when given) when the
+annotations exist, otherwise the synthetic RHD-shaped loader (24 batches unless --num_batches is given). RHD
+coordinates are rescaled to original-image pixels with `* crop_size / hm_size + corner` (:235-240).
 """
 import argparse
 import os
@@ -31,7 +34,8 @@ def parse_args():
     p.add_argument('--is_vis', default=0, type=int)
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--model_path', default='', type=str)
-    p.add_argument('--num_batches', default=24, type=int, help='synthetic loader length')
+    p.add_argument('--num_batches', default=None, type=int,
+                   help='batches to evaluate (synthetic loader: default 24; a real dataset: every batch)')
     return p.parse_args()
 
 
@@ -47,11 +51,13 @@ def main():
     c = cfg.clone()
     c.defrost()
     c.TEST.IMAGES_PER_GPU = args.batch_size
-    loader = list(make_dataloader(c, False, num_batches=args.num_batches).values())[0]
+    loader = list(make_dataloader(c, False, num_batches=24 if args.num_batches is None else args.num_batches,
+                                  max_batches=args.num_batches).values())[0]
     K = cfg.MODEL.NUM_JOINTS
     # accumulators and file formats of the reference (tools/evaluate_2D.py:166-169,270-294): per-joint error
     # sums, PCK counted with a strict `<` over all visible joints, PCK2d.txt = two rows (thresholds, PCK);
-    # coordinates are scaled from heat-map pixels to the input crop (:241-245 with orig size = crop size)
+    # coordinates are scaled from heat-map pixels to original-image pixels with the batch's crop_size / corner (RHD,
+    # :235-240), or to the input crop for the synthetic loader (:241-245 with orig size = crop size)
     acc = Eval2DAccumulator(K, cfg.MODEL.HEATMAP_SIZE[0])
     crop = (cfg.MODEL.IMAGE_SIZE[0], cfg.MODEL.IMAGE_SIZE[1])
     timed, t_total = 0, 0.0
@@ -66,7 +72,11 @@ def main():
             if i >= 20 or i >= len(loader) // 2:
                 t_total += time.time() - t0
                 timed += imgs.shape[0]
-            acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(), orig_size=crop)
+            if 'crop_size' in ret:
+                acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(),
+                        crop_size=ret['crop_size'].numpy(), corner=ret['corner'].numpy())
+            else:
+                acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(), orig_size=crop)
     out_dir = os.path.join(cfg.OUTPUT_DIR or 'output', 'eval2D_results_' + cfg.EXP_NAME)
     mse_each, pck = acc.save(out_dir)
     print('fps: {:.1f}'.format(timed / max(t_total, 1e-9)))

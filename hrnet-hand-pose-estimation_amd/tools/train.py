@@ -6,8 +6,11 @@
 cfg -> eval(cfg.MODEL.NAME + '.get_pose_net') -> criterion dict -> optimizer -> MultiStepLR ->
 core.function.train / validate per epoch -> checkpoint.pth.tar / model_best.pth.tar /
 final_state.pth.tar (tools/train.py:126-405). One process per GPU; multi-GPU = RCCL all-reduce of the
-flat gradient overlapped with backward (hipnet.optim.GradSync), not DataParallel. Data is the
-synthetic RHD-shaped loader (dataset/build.py) since no dataset ships with the repository.
+flat gradient overlapped with backward (hipnet.optim.GradSync), not DataParallel. Data: the RHD
+reader (dataset/rhd.py) when <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle exists - DATASET.DATASET with TRAIN_SET
+for training (shuffled, this rank's share), TEST_DATASET with TEST_SET for validation (every sample, with heat
+maps) - otherwise the synthetic RHD-shaped loader (dataset/build.py). --batches-per-epoch caps a real epoch only
+when given; the synthetic loader is 8 batches (validation 2) unless it is given.
 """
 import argparse
 import os
@@ -33,7 +36,8 @@ def parse_args():
     p.add_argument('--dist-url', default='tcp://127.0.0.1:23456', type=str)
     p.add_argument('--rank', default=0, type=int)
     p.add_argument('--local_rank', default=0, type=int)
-    p.add_argument('--batches-per-epoch', default=8, type=int, help='synthetic loader length')
+    p.add_argument('--batches-per-epoch', default=None, type=int,
+                   help='batches per training epoch (synthetic loader: default 8; a real dataset: every batch)')
     return p.parse_args()
 
 
@@ -86,8 +90,10 @@ def main():
     def lr_at(epoch):
         return cfg.TRAIN.LR * (cfg.TRAIN.LR_FACTOR ** sum(epoch >= s for s in cfg.TRAIN.LR_STEP))
 
-    train_loader = make_dataloader(cfg, True, world > 1, args.batches_per_epoch, rank, world)
-    valid_loader = make_dataloader(cfg, False, world > 1, max(1, args.batches_per_epoch // 4), rank, world)
+    synthetic_batches = 8 if args.batches_per_epoch is None else args.batches_per_epoch
+    train_loader = make_dataloader(cfg, True, world > 1, synthetic_batches, rank, world,
+                                   max_batches=args.batches_per_epoch)
+    valid_loader = make_dataloader(cfg, False, world > 1, max(1, synthetic_batches // 4), rank, world, heatmaps=True)
     for epoch in range(begin_epoch, cfg.TRAIN.END_EPOCH):
         for g in optimizer.param_groups:          # MultiStepLR(LR_STEP, LR_FACTOR)
             g['lr'] = lr_at(epoch)

@@ -548,6 +548,22 @@ int hrnet_resize_normalize_u8(const unsigned char* src, int64_t src_bytes, const
                               int bgr, hr_stream_t stream);
 
 /*
+ * Training input step of the RHD reader (lib/dataset/rhd.py; reference RandomAffineTransform + RandomHorizontalFlip +
+ * ToTensor + Normalize, lib/dataset/transforms/transforms.py:54-175): crops in ONE device buffer of src_bytes bytes
+ * -> out_nchw [n,3,Ho,Wo] f32. slots is the DEVICE slot table of hrnet_resize_normalize_u8 (a crop is a slot whose
+ * offset points at its top-left byte inside the image, with the image's row pitch); inv_mats is a DEVICE table
+ * f32 [n][6]: the 2x3 inverse matrix (output pixel -> slot pixel, row-major) of each slot, flip folded in. Per
+ * output pixel: the mapped position in f64, a bilinear blend in f32 in which each neighbour outside [0,W) x [0,H)
+ * of the slot contributes 0 (cv2 BORDER_CONSTANT 0), rounded half to even and clamped to a u8 code, then
+ * (u/255 - mean[c]) / std[c] as hrnet_normalize_u8 (bit-identical to it for an identity matrix at Ho == H,
+ * Wo == W). A row outside the buffer, or with H, W < 1 or pitch < 3*W, is not read: its output plane is NaN.
+ * mean3/std3 are HOST arrays of 3 floats.
+ */
+int hrnet_affine_warp_normalize_u8(const unsigned char* src, int64_t src_bytes, const int64_t* slots,
+                                   const float* inv_mats, int n, float* out_nchw, int Ho, int Wo, const float* mean3,
+                                   const float* std3, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
