@@ -40,13 +40,18 @@ class Eval2DAccumulator(object):
         self.mse = np.zeros(n_joints)
         self.vis = np.zeros(n_joints)
 
-    def add(self, pred, gt, visibility, crop_size=None, corner=None, orig_size=None):
+    def add(self, pred, gt, visibility, crop_size=None, corner=None, orig_size=None, inverse=None):
         """pred / gt (B,K,2) in heat-map pixels; visibility (B,K[,1]); RHD: crop_size (B,), corner (B,2);
-        otherwise orig_size = (width, height) of the image the coordinates are scaled to"""
+        MHP: inverse (B,2,3), heat-map pixel -> original-image pixel; otherwise orig_size = (width, height) of the
+        image the coordinates are scaled to"""
         pred = np.asarray(pred, dtype=np.float64)
         gt = np.asarray(gt, dtype=np.float64)
         vis = np.asarray(visibility, dtype=np.float64).reshape(pred.shape[0], self.K)
-        if crop_size is not None:
+        if inverse is not None:
+            m = np.asarray(inverse, dtype=np.float64).reshape(-1, 2, 3)
+            pred = np.einsum('bij,bkj->bki', m[:, :, :2], pred) + m[:, None, :, 2]
+            gt = np.einsum('bij,bkj->bki', m[:, :, :2], gt) + m[:, None, :, 2]
+        elif crop_size is not None:
             cs = np.asarray(crop_size, dtype=np.float64).reshape(-1, 1, 1) / self.hm_size
             co = np.asarray(corner, dtype=np.float64).reshape(-1, 1, 2)
             pred, gt = pred * cs + co, gt * cs + co

@@ -8,7 +8,8 @@ the multi-view / temporal / CPM branches belong to other model families.
 
 `validate` also accepts 'RHD' (the evaluation-set reader, dataset/rhd.py; tools/train.py serves it with heat
 maps). The reference's validate skips that name (function.py:800), so validating on the shipped RHD yaml's
-TEST_DATASET did nothing there; here it computes the validation losses.
+TEST_DATASET did nothing there; here it computes the validation losses. 'MHP' (dataset/mhp.py) is accepted
+the same way.
 
 `debug`: the reference hard-codes a module-level `debug = True` that stops every epoch after 5
 iterations (function.py:22,193,812). Here it defaults to False; set `core.function.debug = True`
@@ -23,7 +24,7 @@ from utils.heatmap_decoding import get_final_preds
 debug = False
 
 GENERIC_DATASETS = ('HandGraph_kpt', 'RHD_kpt', 'FreiHand_kpt', 'MHP_kpt', 'MHP_CPM_kpt', 'MHP_seq', 'synthetic_kpt')
-VALID_DATASETS = GENERIC_DATASETS + ('RHD',)
+VALID_DATASETS = GENERIC_DATASETS + ('RHD', 'MHP')
 
 _LOSS_NAMES = (('heatmap_loss', 'WITH_HEATMAP_LOSS', 'HeatmapLoss', 'heatmap_loss'),
                ('pose2d_loss', 'WITH_POSE2D_LOSS', 'Pose2DLoss', 'pose2d_loss'))

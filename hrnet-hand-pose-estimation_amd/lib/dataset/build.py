@@ -2,7 +2,8 @@
 
 make_dataloader builds the named datasets (DATASET.DATASET with TRAIN_SET for training, TEST_DATASET with TEST_SET
 otherwise) when they are RHD readers (dataset/rhd.py: RHD_kpt, RHD) and <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle
-exists. Otherwise it logs one warning naming what is missing and returns the synthetic RHD-shaped loader: it yields
+exists, or MHP readers (dataset/mhp.py: MHP_kpt, MHP, MHP_seq) and <DATA_DIR>/MHP/annotated_frames exists.
+Otherwise it logs one warning naming what is missing and returns the synthetic RHD-shaped loader: it yields
 the sample dict of the reference's RHD key-point dataset (lib/dataset/RHDDatasetKeypoints.py:126-134) from the
 portable generator in hipnet/synth.py, so the tests and bench.py run without a dataset.
 
@@ -14,7 +15,7 @@ import os
 
 import torch
 
-from dataset import rhd
+from dataset import mhp, rhd
 from hipnet import synth
 
 logger = logging.getLogger(__name__)
@@ -61,14 +62,17 @@ class SyntheticLoader(object):
 
 def make_dataloader(cfg, is_train=True, distributed=False, num_batches=8, rank=0, world=1, max_batches=None,
                     heatmaps=None):
-    """{dataset name: loader}. heatmaps=None: RHD_kpt batches carry heat maps and RHD batches do not; True / False
-    forces it (tools/train.py validates on RHD with heat maps)."""
+    """{dataset name: loader}. heatmaps=None: RHD_kpt, MHP_kpt and MHP_seq batches carry heat maps, RHD and MHP
+    batches do not; True / False forces it (tools/train.py validates with heat maps)."""
     names = list(cfg.DATASET.DATASET if is_train else cfg.DATASET.TEST_DATASET)
     subset = cfg.DATASET.TRAIN_SET if is_train else cfg.DATASET.TEST_SET
-    anno = rhd.annotation_path(cfg.DATA_DIR, subset)
-    unknown = [n for n in names if n not in rhd.READERS]
+    if names and all(n in mhp.READERS for n in names):
+        module, anno = mhp, mhp.frames_dir(cfg.DATA_DIR)
+    else:
+        module, anno = rhd, rhd.annotation_path(cfg.DATA_DIR, subset)
+    unknown = [n for n in names if n not in module.READERS]
     if names and not unknown and os.path.exists(anno):
-        return {n: rhd.make_loader(cfg, n, subset, is_train, rank, world, distributed, max_batches, heatmaps)
+        return {n: module.make_loader(cfg, n, subset, is_train, rank, world, distributed, max_batches, heatmaps)
                 for n in names}
     why = 'no reader for {}'.format(unknown) if unknown else 'no datasets named' if not names else \
         '{} not found'.format(anno)

@@ -1,0 +1,336 @@
+"""MHP readers: the reference's MHP (lib/dataset/MHPDataset.py:46-126), MHP_kpt (MHPDatasetKeypoints.py:47-80) and
+MHP_seq (MHPSeqDataset.py:48-240), with the RHD transforms (dataset/rhd.py) applied to the whole 640 x 480 frame.
+
+Layout: <DATA_DIR>/MHP/annotated_frames/data_N/<f>_webcam_<c>.jpg, annotations/data_N/<f>_joints.txt (a name, then
+x y z per line) and calibrations/data_N/webcam_<c>/{rvec,tvec}.pkl (pickles read with encoding='latin1').
+
+Split of the work, as in the RHD reader:
+- DataLoader workers (numpy and PIL only, never the GPU): read the joints and the calibration, project, draw the
+  augmentation, build the float64 matrices; the batch's collate decodes every distinct frame ONCE, packs them into
+  one u8 buffer and gives each slot a table row pointing at its frame (several slots may share one frame).
+- The main process (dataset/rhd.py RHDLoader): one pinned upload, ONE hrnet_affine_warp_normalize_u8 launch,
+  HeatmapGenerator for the targets.
+
+MHP / MHP_kpt: one sample per image. The list is every `*_webcam_<digit>*` file, natural-sorted; training takes the
+first 80 % (int(len * 0.8)), evaluation the rest. The 3-D joints are reordered by idx_MHP and projected with the
+camera's rvec / tvec, K and the distortion (k1, k2, p1, p2, k3); a joint outside the 640 x 480 frame is not visible.
+Reference quirk kept: these readers cv2.imread without cvtColor, so the network sees BGR (the worker swaps the
+channels while packing). MHP_kpt carries heat maps, MHP does not.
+
+MHP_seq: training reads data_1..16, evaluation data_17..21. A directory of n = files // 4 frames gives the centres
+0, STRIDE, 2 STRIDE, ... < n, i.e. (n - 1) // STRIDE + 1 samples; window frame j is clamp(centre + SEQ_IDX[j], 0, n-1)
+for views 1..4. Images are RGB, the distortion is zero, the rotation is Rodrigues(rvec). The batch is what the model
+and the loss consume: `imgs` (5 * 4 * B, 3, H, W) frame-major, slot (j * B + b) * 4 + (c - 1) (the reference's Aggr
+reorder, function.py:35-51); `pose2d`, `visibility` and `heatmaps` (4 * B, 21, ...) are those of the centre frame's
+four views. Augmentation, when on, is drawn per image (5 x 4 draws per sample), as the reference's transform is called
+once per image.
+
+Every batch also carries `hm_inverse` (N, 2, 3) float64: heat-map pixel -> original-image pixel, the inverse of the
+sample's heat-map matrix with the flip folded in. tools/evaluate_2D.py maps predictions and ground truth back through
+it; the reference scales x by 640/64 and y by 480/64 there (evaluate_2D.py:240-245), which does not invert its own
+'short'-scale transform (that crops the frame's central 480 x 480 square).
+
+Deviations, all deliberate:
+- the reference's MHPSeqDataset ignores its index and walks a per-process cursor, and its `last_ret` reuse
+  (:216-231) shifts the cached window by one frame, not by STRIDE: at STRIDE 2 the centre slot holds frame c-1 with
+  the labels of frame c-2. Here index i maps to one fixed (directory, centre) and the window is exact, which makes
+  shuffling, DistributedSampler and several workers possible;
+- the reference's build_dataset passes `transforms=`, which neither MHP class accepts; the transforms here are the RHD
+  ones from the same cfg (augmentation only under WITH_DATA_AUG in training, seeded by (seed, epoch, index));
+- MHP / MHP_kpt list <DATA_DIR>/MHP/annotated_frames (the reference walks all of DATA_DIR); MHP_seq skips a data_N of
+  its range that does not exist (the reference raises) and raises when none does;
+- SCALE_AWARE_SIGMA is refused and `orig_imgs` is not in the batch, as in the RHD reader;
+- a frame that does not decode to 640 x 480 raises ValueError naming the file;
+- cv2 is not used: Rodrigues and projectPoints are restated below in float64 numpy from OpenCV's documented model
+  (pinhole plus k1, k2, p1, p2, k3) and are not pinned against cv2 itself.
+"""
+import fnmatch
+import os
+import pickle
+import re
+
+import numpy as np
+import torch
+
+from dataset.preprocess import pack_images, read_image_rgb
+from dataset.rhd import RHDLoader, augment_from_cfg, draw_params, geometry, transform_joints
+
+# reference lib/dataset/standard_legends.py:31
+IDX_MHP = (20, 17, 16, 18, 19, 1, 0, 2, 3, 5, 4, 6, 7, 13, 12, 14, 15, 9, 8, 10, 11)
+# reference MHPDataset.py:69-77
+INTRINSIC = np.array([[614.878, 0, 313.219], [0, 615.479, 231.288], [0, 0, 1]])
+DISTORTION = np.array([0.092701, -0.175877, -0.0035687, -0.00302299, 0])
+FRAME_W, FRAME_H = 640, 480
+VIEWS = (1, 2, 3, 4)
+SEQ_RANGES = {'train': range(1, 17), 'training': range(1, 17)}
+SEQ_RANGES.update({k: range(17, 22) for k in ('eval', 'valid', 'val', 'evaluation', 'validation')})
+
+
+def frames_dir(data_dir):
+    return os.path.join(data_dir, 'MHP', 'annotated_frames')
+
+
+def natural_sort(names):
+    """the reference's natural_sort (MHPDataset.py:21-24)"""
+    def key(text):
+        return [int(c) if c.isdigit() else c.lower() for c in re.split('([0-9]+)', text)]
+    return sorted(names, key=key)
+
+
+def list_images(root):
+    """every `*_webcam_<digit>*` file under root, natural-sorted (recursive_glob + natural_sort of the reference)"""
+    found = []
+    for d, _dirs, files in os.walk(root):
+        found.extend(os.path.join(d, f) for f in fnmatch.filter(files, '*_webcam_[0-9]*'))
+    return natural_sort(found)
+
+
+def split_range(n, subset):
+    """(start, end) of a subset of n images: the first 80 % train, the rest evaluate (MHPDataset.py:60-68)"""
+    if subset in ('train', 'training'):
+        return 0, int(n * 0.8)
+    if subset in ('eval', 'valid', 'val', 'evaluation', 'validation'):
+        return int(n * 0.8), n
+    raise ValueError('MHP: unknown subset {!r}'.format(subset))
+
+
+def read_joints(path):
+    """21 x 3 float64 world joints of a <f>_joints.txt, in file order (readAnnotation3D)"""
+    with open(path) as f:
+        rows = [l.split() for l in f if l.strip()]
+    return np.array([(float(r[1]), float(r[2]), float(r[3])) for r in rows], dtype=np.float64)
+
+
+def read_calibration(data_dir, subdir, view):
+    """(rvec, tvec) float64 (3,) of one camera"""
+    d = os.path.join(data_dir, 'MHP', 'calibrations', subdir, 'webcam_{}'.format(view))
+    out = []
+    for name in ('rvec.pkl', 'tvec.pkl'):
+        with open(os.path.join(d, name), 'rb') as f:
+            out.append(np.asarray(pickle.load(f, encoding='latin1'), dtype=np.float64).reshape(3))
+    return tuple(out)
+
+
+def rodrigues(rvec):
+    """3 x 3 rotation of a rotation vector (OpenCV's Rodrigues: angle |r| about r / |r|; the identity at 0)"""
+    r = np.asarray(rvec, dtype=np.float64).reshape(3)
+    theta = np.linalg.norm(r)
+    if theta < np.finfo(np.float64).eps:
+        return np.eye(3)
+    k = r / theta
+    kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.cos(theta) * np.eye(3) + (1 - np.cos(theta)) * np.outer(k, k) + np.sin(theta) * kx
+
+
+def project_points(points, rvec, tvec, K, dist):
+    """N x 3 world points -> N x 2 pixels (OpenCV's projectPoints model): X = R X + t, x' = X / Z,
+    r2 = x'^2 + y'^2, x'' = x' (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 x' y' + p2 (r2 + 2 x'^2),
+    y'' = y' (...) + p1 (r2 + 2 y'^2) + 2 p2 x' y', u = fx x'' + cx, v = fy y'' + cy"""
+    X = np.asarray(points, dtype=np.float64).reshape(-1, 3) @ rodrigues(rvec).T + np.asarray(tvec, np.float64).reshape(3)
+    x, y = X[:, 0] / X[:, 2], X[:, 1] / X[:, 2]
+    k1, k2, p1, p2, k3 = (float(v) for v in np.asarray(dist, dtype=np.float64).reshape(-1)[:5])
+    r2 = x * x + y * y
+    radial = 1 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+    xd = x * radial + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+    yd = y * radial + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+    K = np.asarray(K, dtype=np.float64)
+    return np.stack((K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]), axis=1)
+
+
+def visibility(pose2d, width=FRAME_W, height=FRAME_H):
+    """21 x 1 bool: the joint lies inside the frame (MHPDataset.py:108-112)"""
+    p = np.asarray(pose2d)
+    return ((p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 0] < width) & (p[:, 1] < height))[:, None]
+
+
+def hm_inverse(mat_output, flip, hm_size):
+    """2 x 3: heat-map pixel (after the flip) -> original-image pixel"""
+    inv = np.linalg.inv(np.vstack([mat_output, [0., 0., 1.]]))
+    if flip:
+        inv = inv @ np.array([[-1., 0., hm_size - 1], [0., 1., 0.], [0., 0., 1.]])
+    return inv[:2]
+
+
+def seq_windows(n, stride, seq_idx):
+    """(centres, frames): the centres 0, stride, ... < n and, per centre, the clamped window frames"""
+    centres = np.arange(0, n, stride)
+    frames = np.clip(centres[:, None] + np.asarray(seq_idx)[None], 0, n - 1)
+    return centres, frames
+
+
+class _Base(torch.utils.data.Dataset):
+    """worker side shared by the readers; a key is an index or (index, epoch). __getitem__ returns numpy data and
+    the paths of the frames (decoded by `collate`, once per batch and frame)."""
+    heatmaps = False
+    bgr = False
+
+    def __init__(self, cfg, is_train, seed):
+        if cfg.MODEL.NUM_JOINTS != 21 or cfg.DATASET.NUM_JOINTS != 21:
+            raise ValueError('MHP has 21 joints per hand, the config asks for {}'.format(cfg.MODEL.NUM_JOINTS))
+        self.data_dir = cfg.DATA_DIR
+        self.aug = augment_from_cfg(cfg, is_train)
+        self.input_size, self.hm_size = cfg.MODEL.IMAGE_SIZE[0], cfg.MODEL.HEATMAP_SIZE[0]
+        self.seed = seed
+
+    def _view(self, rng, world, rvec, tvec, dist):
+        """labels and matrices of one image of the whole frame"""
+        pose2d = project_points(world, rvec, tvec, INTRINSIC, dist)
+        params = draw_params(rng, FRAME_H, FRAME_W, self.aug)
+        g = geometry(FRAME_H, FRAME_W, params, self.aug, self.input_size, self.hm_size)
+        return {'inverse': g['inverse'], 'hm_inverse': hm_inverse(g['mat_output'], params['flip'], self.hm_size),
+                'pose2d': transform_joints(pose2d, g['mat_output'], params['flip'], self.hm_size),
+                'visibility': visibility(pose2d)}
+
+
+class MHP(_Base):
+    name = 'MHP'
+    bgr = True
+
+    def __init__(self, cfg, subset, is_train=False, seed=0):
+        _Base.__init__(self, cfg, is_train, seed)
+        images = list_images(frames_dir(cfg.DATA_DIR))
+        start, end = split_range(len(images), subset)
+        self.images = images[start:end]
+        self._calib = {}
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, key):
+        idx, epoch = key if isinstance(key, tuple) else (key, 0)
+        path = self.images[idx]
+        subdir = os.path.basename(os.path.dirname(path))
+        frame, _, view = os.path.splitext(os.path.basename(path))[0].split('_')
+        world = read_joints(os.path.join(self.data_dir, 'MHP', 'annotations', subdir, frame + '_joints.txt'))
+        if (subdir, view) not in self._calib:
+            self._calib[(subdir, view)] = read_calibration(self.data_dir, subdir, view)
+        rvec, tvec = self._calib[(subdir, view)]
+        v = self._view(np.random.default_rng((self.seed, epoch, idx)), world[list(IDX_MHP)], rvec, tvec, DISTORTION)
+        return {'paths': [path], 'frames': 1, 'views': 1, 'inverse': v['inverse'][None],
+                'hm_inverse': v['hm_inverse'][None], 'pose2d': v['pose2d'][None], 'visibility': v['visibility'][None]}
+
+
+class MHP_kpt(MHP):
+    name = 'MHP_kpt'
+    heatmaps = True
+
+
+class MHP_seq(_Base):
+    name = 'MHP_seq'
+    heatmaps = True                      # the reference hands MHP_seq a heat-map generator (build.py:56-62)
+
+    def __init__(self, cfg, subset, is_train=False, seed=0):
+        _Base.__init__(self, cfg, is_train, seed)
+        if subset not in SEQ_RANGES:
+            raise ValueError('MHP_seq: unknown subset {!r}'.format(subset))
+        self.stride, self.seq_idx = int(cfg.DATASET.STRIDE), [int(s) for s in cfg.DATASET.SEQ_IDX]
+        self.centre = self.seq_idx.index(0) if 0 in self.seq_idx else len(self.seq_idx) // 2
+        self.dirs, self.joints, self.calib, self.index = [], {}, {}, []
+        for i in SEQ_RANGES[subset]:
+            subdir = 'data_{}'.format(i)
+            d = os.path.join(frames_dir(cfg.DATA_DIR), subdir)
+            if not os.path.isdir(d):
+                continue
+            n = len(os.listdir(d)) // 4
+            if n < 1:
+                continue
+            self.dirs.append((subdir, n))
+            for view in VIEWS:
+                self.calib[(subdir, view)] = read_calibration(cfg.DATA_DIR, subdir, view)
+            for f in range(n):
+                self.joints[(subdir, f)] = read_joints(os.path.join(cfg.DATA_DIR, 'MHP', 'annotations', subdir,
+                                                                    '{}_joints.txt'.format(f)))[list(IDX_MHP)]
+            centres, frames = seq_windows(n, self.stride, self.seq_idx)
+            self.index.extend((len(self.dirs) - 1, int(c), [int(x) for x in w]) for c, w in zip(centres, frames))
+        if not self.dirs:
+            raise ValueError('MHP_seq: no data_N of {} under {}'.format(list(SEQ_RANGES[subset]),
+                                                                      frames_dir(cfg.DATA_DIR)))
+
+    def __len__(self):
+        return len(self.index)
+
+    def window(self, idx):
+        """(directory, centre frame, the window's frames)"""
+        d, c, w = self.index[idx]
+        return self.dirs[d][0], c, w
+
+    def __getitem__(self, key):
+        idx, epoch = key if isinstance(key, tuple) else (key, 0)
+        subdir, centre, frames = self.window(idx)
+        rng = np.random.default_rng((self.seed, epoch, idx))
+        paths, views = [], []
+        for f in frames:
+            for c in VIEWS:
+                paths.append(os.path.join(frames_dir(self.data_dir), subdir, '{}_webcam_{}.jpg'.format(f, c)))
+                rvec, tvec = self.calib[(subdir, c)]
+                # the window frame's image is mapped with its own draw; the labels are the centre frame's
+                views.append(self._view(rng, self.joints[(subdir, centre)], rvec, tvec, np.zeros(5)))
+        V = len(VIEWS)
+        mid = slice(self.centre * V, (self.centre + 1) * V)
+        stack = lambda k, s=slice(None): np.stack([v[k] for v in views[s]])
+        return {'paths': paths, 'frames': len(frames), 'views': V, 'inverse': stack('inverse'),
+                'hm_inverse': stack('hm_inverse', mid), 'pose2d': stack('pose2d', mid),
+                'visibility': stack('visibility', mid)}
+
+
+READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq}
+
+
+def decode(path, bgr):
+    img = read_image_rgb(path)
+    if img.shape[:2] != (FRAME_H, FRAME_W):
+        raise ValueError('{}: {} x {} px, MHP frames are {} x {}'.format(path, img.shape[1], img.shape[0], FRAME_W,
+                                                                          FRAME_H))
+    return img[:, :, ::-1] if bgr else img
+
+
+def slot_order(batch, frames, views):
+    """slot of image (b, j, v) of a batch: (j * batch + b) * views + v, frame-major"""
+    b, j, v = np.meshgrid(np.arange(batch), np.arange(frames), np.arange(views), indexing='ij')
+    return ((j * batch + b) * views + v).reshape(batch, frames * views)
+
+
+def collate(samples, bgr=False):
+    """worker side: every distinct frame of the batch decoded once and packed into one u8 CPU buffer; a slot table
+    row per image (rows of a shared frame point at the same bytes), in slot_order; the f32 inverse matrices; the
+    labels stacked over (sample, view)"""
+    F, V = samples[0]['frames'], samples[0]['views']
+    order = slot_order(len(samples), F, V)
+    unique, where = [], {}
+    for s in samples:
+        for p in s['paths']:
+            if p not in where:
+                where[p] = len(unique)
+                unique.append(p)
+    packed = pack_images([decode(p, bgr) for p in unique], pin=False)
+    n = len(samples) * F * V
+    table = torch.empty((n, 4), dtype=torch.int64)
+    inverse = np.empty((n, 2, 3))
+    for b, s in enumerate(samples):
+        slots = torch.from_numpy(order[b])
+        table[slots] = packed.table[[where[p] for p in s['paths']]]
+        inverse[order[b]] = s['inverse']
+    cat = lambda k: np.concatenate([s[k] for s in samples])
+    return {'buffer': packed.buffer, 'table': table,
+            'inverse': torch.from_numpy(inverse.astype(np.float32).reshape(-1, 6)),
+            'pose2d': torch.from_numpy(cat('pose2d').astype(np.float32)),
+            'visibility': torch.from_numpy(cat('visibility')),
+            'hm_inverse': torch.from_numpy(cat('hm_inverse'))}
+
+
+def collate_bgr(samples):
+    return collate(samples, bgr=True)
+
+
+def collate_rgb(samples):
+    return collate(samples, bgr=False)
+
+
+def make_loader(cfg, name, subset, is_train, rank=0, world=1, distributed=False, max_batches=None, heatmaps=None):
+    dataset = READERS[name](cfg, subset, is_train=is_train)
+    fn = collate_bgr if dataset.bgr else collate_rgb
+    if is_train:
+        return RHDLoader(cfg, dataset, cfg.TRAIN.IMAGES_PER_GPU, True, rank if distributed else 0,
+                         world if distributed else 1, max_batches, heatmaps, collate_fn=fn)
+    return RHDLoader(cfg, dataset, cfg.TEST.IMAGES_PER_GPU, False, max_batches=max_batches, heatmaps=heatmaps,
+                     collate_fn=fn)

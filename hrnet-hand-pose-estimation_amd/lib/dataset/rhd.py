@@ -263,10 +263,13 @@ class _EpochBatches(object):
 
 class RHDLoader(object):
     """main-process side: iterable of device batches {'imgs', ['heatmaps'], 'pose2d', 'visibility', 'corner',
-    'crop_size'} with the attributes the loops use (`batch_size`, `dataset`, `sampler.set_epoch`, `len`)"""
+    'crop_size'} with the attributes the loops use (`batch_size`, `dataset`, `sampler.set_epoch`, `len`).
+    `collate_fn` (a module-level function: spawned workers import it) packs a worker batch into {'buffer', 'table',
+    'inverse', ...}; every other key it returns reaches the device batch as it is (dataset/mhp.py adds
+    'hm_inverse')."""
 
     def __init__(self, cfg, dataset, batch_size, shuffle, rank=0, world=1, max_batches=None, heatmaps=None,
-                 workers=None, seed=0):
+                 workers=None, seed=0, collate_fn=None):
         self.dataset, self.batch_size = dataset, batch_size
         self.heatmaps = dataset.heatmaps if heatmaps is None else bool(heatmaps)
         self.num_joints, self.sigma = cfg.MODEL.NUM_JOINTS, cfg.DATASET.SIGMA
@@ -284,7 +287,7 @@ class RHDLoader(object):
             kw = {'multiprocessing_context': 'spawn', 'persistent_workers': True}
         self.loader = torch.utils.data.DataLoader(dataset, batch_sampler=_EpochBatches(self.sampler, batch_size,
                                                                                        max_batches),
-                                                  num_workers=workers, collate_fn=collate, **kw)
+                                                  num_workers=workers, collate_fn=collate_fn or collate, **kw)
         self._staging, self._copied, self._next = [None, None], [None, None], 0
 
     def __len__(self):
@@ -313,8 +316,9 @@ class RHDLoader(object):
         if self.heatmaps:
             joints = torch.cat((b['pose2d'], b['visibility'].float()), 2).pin_memory().to(dev, non_blocking=True)
             out['heatmaps'] = HeatmapGenerator(self.hm_res, self.num_joints, self.sigma)(joints)
-        for key in ('pose2d', 'visibility', 'corner', 'crop_size'):
-            out[key] = b[key]
+        for key in b:
+            if key not in ('buffer', 'table', 'inverse'):
+                out[key] = b[key]
         return out
 
 

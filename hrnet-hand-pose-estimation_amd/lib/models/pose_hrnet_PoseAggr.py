@@ -65,6 +65,8 @@ class PoseHighResolutionNet(_SoftmaxNet):
         self.use_warping_test = bool(cfg.MODEL.USE_WARPING_TEST)
         self.is_train = is_train
         self.flag = (is_train and self.use_warping_train) or (not is_train and self.use_warping_test)   # reference :293
+        # training the head: its gradients are autograd .grad tensors, not the flat buffer (utils.get_optimizer)
+        self.autograd_grads = bool(is_train and self.use_warping_train)
         nj = int(cfg.MODEL.NUM_JOINTS)
         self.num_joints = nj
         self.dilation_rates = [int(d) for d in cfg.MODEL.DILATION_RATES]

@@ -41,7 +41,10 @@ def get_optimizer(cfg, model):
     # trains through the recorded programs. A model with frozen parameters (pose_hrnet_PoseAggr freezes its backbone,
     # reference pose_hrnet_PoseAggr.py:647-730, and its head's gradients arrive as autograd .grad tensors) gets the
     # torch optimiser over the parameters that require gradients, as the reference builds it (utils.py:83).
+    # A model whose gradients arrive as autograd .grad tensors outside the flat buffer (pose_hrnet_PoseAggr training
+    # its head, `autograd_grads`) gets it as well, frozen parameters or not: FlatAdam would never see them.
     frozen = any(not p.requires_grad for n, p in inner.named_parameters() if n != 'trainable_temp')
+    frozen = frozen or getattr(inner, 'autograd_grads', False)
     if name == 'adam' and hasattr(inner, 'hip') and not frozen and os.environ.get('HRNET_TORCH_OPTIM', '0') != '1':
         from hipnet.optim import FlatAdam
         return FlatAdam(inner, lr=cfg.TRAIN.LR, weight_decay=cfg.TRAIN.WD)

@@ -8,7 +8,10 @@ visibility, PCK for thresholds 1..49 px, fps after 20 warm-up iterations; writes
 mse2d_each_joint.txt and PCK2d.txt (tools/evaluate_2D.py:172-294). Data: TEST_DATASET / TEST_SET through
 dataset/build.py - the RHD reader (every sample, in order; --num_batches caps it only when given) when the
 annotations exist, otherwise the synthetic RHD-shaped loader (24 batches unless --num_batches is given). RHD
-coordinates are rescaled to original-image pixels with `* crop_size / hm_size + corner` (:235-240).
+coordinates are rescaled to original-image pixels with `* crop_size / hm_size + corner` (:235-240). The MHP readers
+(dataset/mhp.py: MHP, MHP_kpt, MHP_seq) serve <DATA_DIR>/MHP; their batches carry `hm_inverse`, the inverse of each
+sample's heat-map matrix, and the coordinates are mapped back through it. The reference scales MHP by 640/64 and
+480/64 instead (:241-245), which does not invert its own 'short'-scale crop of the frame.
 """
 import argparse
 import os
@@ -57,7 +60,8 @@ def main():
     # accumulators and file formats of the reference (tools/evaluate_2D.py:166-169,270-294): per-joint error
     # sums, PCK counted with a strict `<` over all visible joints, PCK2d.txt = two rows (thresholds, PCK);
     # coordinates are scaled from heat-map pixels to original-image pixels with the batch's crop_size / corner (RHD,
-    # :235-240), or to the input crop for the synthetic loader (:241-245 with orig size = crop size)
+    # :235-240) or its hm_inverse matrices (MHP), or to the input crop for the synthetic loader (:241-245 with orig
+    # size = crop size)
     acc = Eval2DAccumulator(K, cfg.MODEL.HEATMAP_SIZE[0])
     crop = (cfg.MODEL.IMAGE_SIZE[0], cfg.MODEL.IMAGE_SIZE[1])
     timed, t_total = 0, 0.0
@@ -72,7 +76,10 @@ def main():
             if i >= 20 or i >= len(loader) // 2:
                 t_total += time.time() - t0
                 timed += imgs.shape[0]
-            if 'crop_size' in ret:
+            if 'hm_inverse' in ret:
+                acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(),
+                        inverse=ret['hm_inverse'].numpy())
+            elif 'crop_size' in ret:
                 acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(),
                         crop_size=ret['crop_size'].numpy(), corner=ret['corner'].numpy())
             else:

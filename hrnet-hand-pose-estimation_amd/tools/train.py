@@ -9,7 +9,8 @@ final_state.pth.tar (tools/train.py:126-405). One process per GPU; multi-GPU = R
 flat gradient overlapped with backward (hipnet.optim.GradSync), not DataParallel. Data: the RHD
 reader (dataset/rhd.py) when <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle exists - DATASET.DATASET with TRAIN_SET
 for training (shuffled, this rank's share), TEST_DATASET with TEST_SET for validation (every sample, with heat
-maps) - otherwise the synthetic RHD-shaped loader (dataset/build.py). --batches-per-epoch caps a real epoch only
+maps) - or the MHP readers (dataset/mhp.py: MHP_kpt, MHP, and MHP_seq for pose_hrnet_PoseAggr) when
+<DATA_DIR>/MHP/annotated_frames exists - otherwise the synthetic RHD-shaped loader (dataset/build.py). --batches-per-epoch caps a real epoch only
 when given; the synthetic loader is 8 batches (validation 2) unless it is given.
 """
 import argparse
