@@ -2,7 +2,7 @@
 
 make_dataloader builds the named datasets (DATASET.DATASET with TRAIN_SET for training, TEST_DATASET with TEST_SET
 otherwise) when they are RHD readers (dataset/rhd.py: RHD_kpt, RHD) and <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle
-exists, or MHP readers (dataset/mhp.py: MHP_kpt, MHP, MHP_seq) and <DATA_DIR>/MHP/annotated_frames exists.
+exists, or MHP readers (dataset/mhp.py: MHP_kpt, MHP, MHP_seq, MHP_mv) and <DATA_DIR>/MHP/annotated_frames exists.
 Otherwise it logs one warning naming what is missing and returns the synthetic RHD-shaped loader: it yields
 the sample dict of the reference's RHD key-point dataset (lib/dataset/RHDDatasetKeypoints.py:126-134) from the
 portable generator in hipnet/synth.py, so the tests and bench.py run without a dataset.

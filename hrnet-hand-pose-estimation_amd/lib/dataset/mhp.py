@@ -1,5 +1,6 @@
-"""MHP readers: the reference's MHP (lib/dataset/MHPDataset.py:46-126), MHP_kpt (MHPDatasetKeypoints.py:47-80) and
-MHP_seq (MHPSeqDataset.py:48-240), with the RHD transforms (dataset/rhd.py) applied to the whole 640 x 480 frame.
+"""MHP readers: the reference's MHP (lib/dataset/MHPDataset.py:46-126), MHP_kpt (MHPDatasetKeypoints.py:47-80),
+MHP_seq (MHPSeqDataset.py:48-240) and MHP_mv (MHPMultiViewDataset.py:31-216), with the RHD transforms
+(dataset/rhd.py) applied to the whole 640 x 480 frame.
 
 Layout: <DATA_DIR>/MHP/annotated_frames/data_N/<f>_webcam_<c>.jpg, annotations/data_N/<f>_joints.txt (a name, then
 x y z per line) and calibrations/data_N/webcam_<c>/{rvec,tvec}.pkl (pickles read with encoding='latin1').
@@ -25,6 +26,19 @@ reorder, function.py:35-51); `pose2d`, `visibility` and `heatmaps` (4 * B, 21, .
 four views. Augmentation, when on, is drawn per image (5 x 4 draws per sample), as the reference's transform is called
 once per image.
 
+MHP_mv: the reference's MHPMultiViewDataset (MHPMultiViewDataset.py:31-216), read by tools/evaluate_3D.py. Training
+reads data_1..16, evaluation data_17..21 (a missing directory is skipped, as for MHP_seq); index i is the (directory,
+frame) pair i in natural order, n = files // 4 frames per directory; the views are 1..4 or the subset passed as
+`views`. Images are RGB (the reference calls cvtColor here), the distortion is zero (:90). A sample is frames = 1,
+views = V, so batch slot b * V + v. Besides `buffer` / `table` / `inverse` the batch carries `pose2d` (B*V, 21, 2) in
+heat-map pixels, `visibility` (B*V, 21, 1), `hm_inverse` (B*V, 2, 3), and stacked per sample `pose3d` (B, 21, 3) (the
+idx_MHP-reordered world joints), `extrinsic_matrices` (B, V, 3, 4) = [R | t] and `intrinsic_matrix` (B, 3, 3), all
+float64. The reference's occlusion (:168-180) is kept, in evaluation too: for image (i, c) the generator
+random.Random(4 i + c) (the sequence of random.seed(4 i + c)) draws j = randint(0, 20); the centre is the frame-pixel
+projection of joint j truncated to int; `collate` paints a black disc of radius 50 on the decoded frame, and a joint
+within 50 px of the centre (np.linalg.norm(p - centre) <= 50) is invisible, like one outside the frame. cv2.circle's
+rasterisation is not available: the painted pixels are those with (x - cx)^2 + (y - cy)^2 <= 50^2 (unpinned).
+
 Every batch also carries `hm_inverse` (N, 2, 3) float64: heat-map pixel -> original-image pixel, the inverse of the
 sample's heat-map matrix with the flip folded in. tools/evaluate_2D.py maps predictions and ground truth back through
 it; the reference scales x by 640/64 and y by 480/64 there (evaluate_2D.py:240-245), which does not invert its own
@@ -41,12 +55,16 @@ Deviations, all deliberate:
   its range that does not exist (the reference raises) and raises when none does;
 - SCALE_AWARE_SIGMA is refused and `orig_imgs` is not in the batch, as in the RHD reader;
 - a frame that does not decode to 640 x 480 raises ValueError naming the file;
+- MHP_mv: the reference walks a per-process cursor and ignores its index (with num_workers = 8 every worker repeats
+  the same samples); here index i is fixed, as for MHP_seq. `orig_imgs` is left out, the transforms are the RHD ones
+  as for the other MHP readers, and the matrices are float64 (the reference's intrinsics are float32);
 - cv2 is not used: Rodrigues and projectPoints are restated below in float64 numpy from OpenCV's documented model
   (pinhole plus k1, k2, p1, p2, k3) and are not pinned against cv2 itself.
 """
 import fnmatch
 import os
 import pickle
+import random
 import re
 
 import numpy as np
@@ -62,6 +80,7 @@ INTRINSIC = np.array([[614.878, 0, 313.219], [0, 615.479, 231.288], [0, 0, 1]])
 DISTORTION = np.array([0.092701, -0.175877, -0.0035687, -0.00302299, 0])
 FRAME_W, FRAME_H = 640, 480
 VIEWS = (1, 2, 3, 4)
+OCCLUSION_RADIUS = 50          # MHPMultiViewDataset.py:170
 SEQ_RANGES = {'train': range(1, 17), 'training': range(1, 17)}
 SEQ_RANGES.update({k: range(17, 22) for k in ('eval', 'valid', 'val', 'evaluation', 'validation')})
 
@@ -172,6 +191,30 @@ class _Base(torch.utils.data.Dataset):
         self.input_size, self.hm_size = cfg.MODEL.IMAGE_SIZE[0], cfg.MODEL.HEATMAP_SIZE[0]
         self.seed = seed
 
+    def _scan(self, cfg, subset):
+        """the directories data_N of the subset's range (SEQ_RANGES) that exist: self.dirs [(name, frames)], the
+        reordered world joints self.joints[(name, frame)] and the calibrations self.calib[(name, view)]"""
+        if subset not in SEQ_RANGES:
+            raise ValueError('{}: unknown subset {!r}'.format(self.name, subset))
+        self.dirs, self.joints, self.calib = [], {}, {}
+        for i in SEQ_RANGES[subset]:
+            subdir = 'data_{}'.format(i)
+            d = os.path.join(frames_dir(cfg.DATA_DIR), subdir)
+            if not os.path.isdir(d):
+                continue
+            n = len(os.listdir(d)) // 4
+            if n < 1:
+                continue
+            self.dirs.append((subdir, n))
+            for view in VIEWS:
+                self.calib[(subdir, view)] = read_calibration(cfg.DATA_DIR, subdir, view)
+            for f in range(n):
+                self.joints[(subdir, f)] = read_joints(os.path.join(cfg.DATA_DIR, 'MHP', 'annotations', subdir,
+                                                                    '{}_joints.txt'.format(f)))[list(IDX_MHP)]
+        if not self.dirs:
+            raise ValueError('{}: no data_N of {} under {}'.format(self.name, list(SEQ_RANGES[subset]),
+                                                                 frames_dir(cfg.DATA_DIR)))
+
     def _view(self, rng, world, rvec, tvec, dist):
         """labels and matrices of one image of the whole frame"""
         pose2d = project_points(world, rvec, tvec, INTRINSIC, dist)
@@ -179,7 +222,7 @@ class _Base(torch.utils.data.Dataset):
         g = geometry(FRAME_H, FRAME_W, params, self.aug, self.input_size, self.hm_size)
         return {'inverse': g['inverse'], 'hm_inverse': hm_inverse(g['mat_output'], params['flip'], self.hm_size),
                 'pose2d': transform_joints(pose2d, g['mat_output'], params['flip'], self.hm_size),
-                'visibility': visibility(pose2d)}
+                'visibility': visibility(pose2d), 'frame2d': pose2d}
 
 
 class MHP(_Base):
@@ -221,30 +264,13 @@ class MHP_seq(_Base):
 
     def __init__(self, cfg, subset, is_train=False, seed=0):
         _Base.__init__(self, cfg, is_train, seed)
-        if subset not in SEQ_RANGES:
-            raise ValueError('MHP_seq: unknown subset {!r}'.format(subset))
         self.stride, self.seq_idx = int(cfg.DATASET.STRIDE), [int(s) for s in cfg.DATASET.SEQ_IDX]
         self.centre = self.seq_idx.index(0) if 0 in self.seq_idx else len(self.seq_idx) // 2
-        self.dirs, self.joints, self.calib, self.index = [], {}, {}, []
-        for i in SEQ_RANGES[subset]:
-            subdir = 'data_{}'.format(i)
-            d = os.path.join(frames_dir(cfg.DATA_DIR), subdir)
-            if not os.path.isdir(d):
-                continue
-            n = len(os.listdir(d)) // 4
-            if n < 1:
-                continue
-            self.dirs.append((subdir, n))
-            for view in VIEWS:
-                self.calib[(subdir, view)] = read_calibration(cfg.DATA_DIR, subdir, view)
-            for f in range(n):
-                self.joints[(subdir, f)] = read_joints(os.path.join(cfg.DATA_DIR, 'MHP', 'annotations', subdir,
-                                                                    '{}_joints.txt'.format(f)))[list(IDX_MHP)]
+        self._scan(cfg, subset)
+        self.index = []
+        for d, (_subdir, n) in enumerate(self.dirs):
             centres, frames = seq_windows(n, self.stride, self.seq_idx)
-            self.index.extend((len(self.dirs) - 1, int(c), [int(x) for x in w]) for c, w in zip(centres, frames))
-        if not self.dirs:
-            raise ValueError('MHP_seq: no data_N of {} under {}'.format(list(SEQ_RANGES[subset]),
-                                                                      frames_dir(cfg.DATA_DIR)))
+            self.index.extend((d, int(c), [int(x) for x in w]) for c, w in zip(centres, frames))
 
     def __len__(self):
         return len(self.index)
@@ -273,7 +299,69 @@ class MHP_seq(_Base):
                 'visibility': stack('visibility', mid)}
 
 
-READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq}
+class MHP_mv(_Base):
+    """the reference's MHPMultiViewDataset (MHPMultiViewDataset.py:31-216): sample i is frame i of the subset's
+    directories in natural order, seen by the cameras `views` (default 1..4); batch slot b * V + v"""
+    name = 'MHP_mv'
+
+    def __init__(self, cfg, subset, is_train=False, seed=0, views=VIEWS):
+        _Base.__init__(self, cfg, is_train, seed)
+        self.views = tuple(int(c) for c in views)
+        if len(set(self.views)) != len(self.views) or not set(self.views) <= set(VIEWS) or len(self.views) < 2:
+            raise ValueError('MHP_mv: views {} (two or more distinct views of {})'.format(list(views), list(VIEWS)))
+        self._scan(cfg, subset)
+        self.index = [(subdir, f) for subdir, n in self.dirs for f in range(n)]
+
+    def __len__(self):
+        return len(self.index)
+
+    def __getitem__(self, key):
+        idx, epoch = key if isinstance(key, tuple) else (key, 0)
+        subdir, f = self.index[idx]
+        world = self.joints[(subdir, f)]
+        rng = np.random.default_rng((self.seed, epoch, idx))
+        paths, views, discs, extrinsic = [], [], [], []
+        for c in self.views:
+            paths.append(os.path.join(frames_dir(self.data_dir), subdir, '{}_webcam_{}.jpg'.format(f, c)))
+            rvec, tvec = self.calib[(subdir, c)]
+            v = self._view(rng, world, rvec, tvec, np.zeros(5))
+            centre = occlusion_centre(v['frame2d'], idx, c)
+            v['visibility'] = v['visibility'] & ~occluded(v['frame2d'], centre)
+            views.append(v)
+            discs.append(centre)
+            extrinsic.append(np.c_[rodrigues(rvec), tvec])
+        stack = lambda k: np.stack([v[k] for v in views])
+        return {'paths': paths, 'frames': 1, 'views': len(self.views), 'inverse': stack('inverse'),
+                'hm_inverse': stack('hm_inverse'), 'pose2d': stack('pose2d'), 'visibility': stack('visibility'),
+                'occlusion': discs, 'pose3d': world, 'extrinsic_matrices': np.stack(extrinsic),
+                'intrinsic_matrix': INTRINSIC}
+
+
+def occlusion_centre(frame2d, index, view):
+    """(x, y) int centre of the occlusion disc of image (index, view): the frame-pixel joint drawn by
+    random.seed(4 index + view); random.randint(0, 20), truncated to int (MHPMultiViewDataset.py:168-172)"""
+    j = random.Random(4 * index + view).randint(0, 20)
+    return tuple(int(v) for v in np.asarray(frame2d[j]).astype(int))
+
+
+def occluded(frame2d, centre, radius=OCCLUSION_RADIUS):
+    """21 x 1 bool: the joint lies within `radius` of the disc's centre (np.linalg.norm(p - centre) <= radius)"""
+    return (np.linalg.norm(np.asarray(frame2d) - np.asarray(centre), axis=1) <= radius)[:, None]
+
+
+def paint_disc(img, centre, radius=OCCLUSION_RADIUS):
+    """a copy of the u8 frame with every pixel (x, y), (x - cx)^2 + (y - cy)^2 <= radius^2, set to black"""
+    out = np.array(img)
+    cx, cy = centre
+    y0, y1 = max(cy - radius, 0), min(cy + radius + 1, out.shape[0])
+    x0, x1 = max(cx - radius, 0), min(cx + radius + 1, out.shape[1])
+    if y0 < y1 and x0 < x1:
+        yy, xx = np.ogrid[y0:y1, x0:x1]
+        out[y0:y1, x0:x1][(xx - cx) ** 2 + (yy - cy) ** 2 <= radius * radius] = 0
+    return out
+
+
+READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq, 'MHP_mv': MHP_mv}
 
 
 def decode(path, bgr):
@@ -290,32 +378,46 @@ def slot_order(batch, frames, views):
     return ((j * batch + b) * views + v).reshape(batch, frames * views)
 
 
+MULTI_VIEW_KEYS = ('pose3d', 'extrinsic_matrices', 'intrinsic_matrix')
+
+
 def collate(samples, bgr=False):
-    """worker side: every distinct frame of the batch decoded once and packed into one u8 CPU buffer; a slot table
-    row per image (rows of a shared frame point at the same bytes), in slot_order; the f32 inverse matrices; the
-    labels stacked over (sample, view)"""
+    """worker side: every distinct frame of the batch decoded once (with the sample's occlusion disc painted on it,
+    when it carries one) and packed into one u8 CPU buffer; a slot table row per image (rows of a shared frame point
+    at the same bytes), in slot_order; the f32 inverse matrices; the labels stacked over (sample, view); the
+    multi-view extras of MHP_mv stacked over samples"""
     F, V = samples[0]['frames'], samples[0]['views']
     order = slot_order(len(samples), F, V)
     unique, where = [], {}
     for s in samples:
-        for p in s['paths']:
-            if p not in where:
-                where[p] = len(unique)
-                unique.append(p)
-    packed = pack_images([decode(p, bgr) for p in unique], pin=False)
+        discs = s.get('occlusion') or [None] * len(s['paths'])
+        for key in zip(s['paths'], discs):
+            if key not in where:
+                where[key] = len(unique)
+                unique.append(key)
+    frames = []
+    for p, disc in unique:
+        img = decode(p, bgr)
+        frames.append(img if disc is None else paint_disc(img, disc))
+    packed = pack_images(frames, pin=False)
     n = len(samples) * F * V
     table = torch.empty((n, 4), dtype=torch.int64)
     inverse = np.empty((n, 2, 3))
     for b, s in enumerate(samples):
         slots = torch.from_numpy(order[b])
-        table[slots] = packed.table[[where[p] for p in s['paths']]]
+        discs = s.get('occlusion') or [None] * len(s['paths'])
+        table[slots] = packed.table[[where[key] for key in zip(s['paths'], discs)]]
         inverse[order[b]] = s['inverse']
     cat = lambda k: np.concatenate([s[k] for s in samples])
-    return {'buffer': packed.buffer, 'table': table,
-            'inverse': torch.from_numpy(inverse.astype(np.float32).reshape(-1, 6)),
-            'pose2d': torch.from_numpy(cat('pose2d').astype(np.float32)),
-            'visibility': torch.from_numpy(cat('visibility')),
-            'hm_inverse': torch.from_numpy(cat('hm_inverse'))}
+    out = {'buffer': packed.buffer, 'table': table,
+           'inverse': torch.from_numpy(inverse.astype(np.float32).reshape(-1, 6)),
+           'pose2d': torch.from_numpy(cat('pose2d').astype(np.float32)),
+           'visibility': torch.from_numpy(cat('visibility')),
+           'hm_inverse': torch.from_numpy(cat('hm_inverse'))}
+    for k in MULTI_VIEW_KEYS:                          # MHP_mv: one entry per sample, stacked to (B, ...) float64
+        if k in samples[0]:
+            out[k] = torch.from_numpy(np.stack([np.asarray(s[k], dtype=np.float64) for s in samples]))
+    return out
 
 
 def collate_bgr(samples):
@@ -326,8 +428,10 @@ def collate_rgb(samples):
     return collate(samples, bgr=False)
 
 
-def make_loader(cfg, name, subset, is_train, rank=0, world=1, distributed=False, max_batches=None, heatmaps=None):
-    dataset = READERS[name](cfg, subset, is_train=is_train)
+def make_loader(cfg, name, subset, is_train, rank=0, world=1, distributed=False, max_batches=None, heatmaps=None,
+                **reader_kw):
+    """reader_kw reach the reader (MHP_mv: views)"""
+    dataset = READERS[name](cfg, subset, is_train=is_train, **reader_kw)
     fn = collate_bgr if dataset.bgr else collate_rgb
     if is_train:
         return RHDLoader(cfg, dataset, cfg.TRAIN.IMAGES_PER_GPU, True, rank if distributed else 0,

@@ -564,6 +564,21 @@ int hrnet_affine_warp_normalize_u8(const unsigned char* src, int64_t src_bytes, 
                                    const float* std3, hr_stream_t stream);
 
 /*
+ * Multi-view DLT triangulation of tools/evaluate_3D.py (reference tools/evaluate_3D.py:178-190,270-301,
+ * lib/models/triangulation_model_utils/multiview.py:120-187, lib/utils/misc.py:64-97), one thread per (sample, joint):
+ *   pts       [B,V,K,2] f32, slot b*V + v (the order hrnet_decode_* leaves for a (B*V, K, H, W) heat-map batch)
+ *   to_frame  [B*V,2,3] f64 or NULL: affine heat-map pixel -> frame pixel applied first; NULL: pts are frame pixels
+ *   proj      [B,V,3,4] f64: K [R|t]
+ *   conf      [B,V,K] f32 or NULL: a view's two rows are scaled by its weight (multiview.py:142-169)
+ *   X         [B,K,3] f32: right singular vector of the 2V x 4 DLT matrix for its smallest singular value,
+ *             v[0:3] / v[3], in f64 (Givens QR of the rows + one-sided Jacobi SVD; A^T A is never formed)
+ *   pts_frame [B,V,K,2] f32 or NULL: the mapped 2-D points
+ * 2 <= V <= 8. Fewer than two views of nonzero weight give NaN, v[3] = 0 a non-finite X.
+ */
+int hrnet_triangulate(const float* pts, const double* to_frame, const double* proj, const float* conf, float* X,
+                      float* pts_frame, int B, int V, int K, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
