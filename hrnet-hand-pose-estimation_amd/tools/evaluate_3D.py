@@ -1,6 +1,7 @@
 """3-D evaluation on MHP with the reference's flags (tools/evaluate_3D.py:29-60,178-190,270-419):
 
     python tools/evaluate_3D.py --cfg <yaml> --model_path <state_dict.pth.tar> --views '[1,2,3,4]' --batch_size 32
+        [--triangulation {dlt,ransac}] [--ransac_epsilon 25] [--ransac_iters 0] [--seed 0]
 
 cfg -> MODEL.NAME pose_hrnet / pose_hrnet_softmax, strict load ('module.' prefix stripped) -> the multi-view reader
 MHP_mv (dataset/mhp.py) on DATASET.TEST_SET of <DATA_DIR>/MHP, whatever DATASET.TEST_DATASET names (every 2-D MHP
@@ -17,6 +18,20 @@ The reference lifts pose_hrnet predictions with DLT_sii_pytorch (lib/utils/misc.
 iterations from a torch.rand start; this tool computes the vector they converge to (see utils/multiview.py).
 The models alg, ransac, vol, vol_CPM and FTL are not built: they are refused with a ValueError.
 
+--triangulation ransac lifts with the reference's RANSAC over the views instead (lib/utils/misc.py:178-240, called by
+RANSACTriangulationNet.forward, lib/models/triangulation.py:72-118), as a lifting method for the same two models: ONE
+hrnet_triangulate_ransac launch per batch in place of the hrnet_triangulate one (utils/multiview.py). The MHP_mv
+reader paints a disc over one joint per view (dataset/mhp.py), whose prediction in that view is a gross outlier that
+the all-view DLT takes in at full weight; RANSAC drops the views that disagree with the best two-view solution.
+--ransac_epsilon is the reference's threshold in the reference's unit, HALF the frame-pixel distance (25, its value,
+keeps views within 50 px). --ransac_iters 0 (default) tries every pair of views in lexicographic order - deterministic,
+and a superset of what random draws can see; N > 0 tries N random pairs per joint drawn as the reference draws them,
+from --seed (drawn on the host before the timed region; the kernel draws nothing). The four result files keep their
+format; the tool also prints the mean number of inlier views per joint and the share of points dropped per camera, and
+writes ransac_inliers.txt (V x K: the share of frames in which the view was kept for the joint).
+MODEL.DIRECT_OPTIMIZATION true (the reference's scipy Huber refinement of the RANSAC result) is not built and is
+refused with --triangulation ransac.
+
 Reference defects not reproduced:
 - get_final_preds(heatmaps, cfg) (:296) passes the cfg as `use_softmax`, which is always truthy, so every model is
   decoded by expectation; here MODEL.HEATMAP_SOFTMAX chooses, as in tools/evaluate_2D.py;
@@ -27,6 +42,7 @@ Reference defects not reproduced:
 import argparse
 import ast
 import os
+import random
 import sys
 import time
 
@@ -40,7 +56,8 @@ from core.evaluate3d import Eval3DAccumulator, auc
 from dataset import mhp
 from models import pose_hrnet, pose_hrnet_softmax
 from utils.heatmap_decoding import get_final_preds
-from utils.multiview import triangulate_batch_of_points
+from utils.multiview import (MAX_HYPOTHESES, all_view_pairs, sample_view_pairs, triangulate_batch_of_points,
+                             triangulate_ransac_batch)
 
 MODELS = {'pose_hrnet': pose_hrnet.get_pose_net, 'pose_hrnet_softmax': pose_hrnet_softmax.get_pose_net}
 NOT_BUILT = ('alg', 'ransac', 'vol', 'vol_CPM', 'FTL')
@@ -57,7 +74,19 @@ def parse_args(argv=None):
     p.add_argument('--batch_size', default=32, type=int)
     p.add_argument('--model_path', default='', type=str)
     p.add_argument('--num_batches', default=None, type=int, help='batches to evaluate (default: every batch)')
-    return p.parse_args(argv)
+    p.add_argument('--triangulation', default='dlt', choices=('dlt', 'ransac'),
+                   help='lifting: DLT over all views, or RANSAC over the views and DLT over the inliers')
+    p.add_argument('--ransac_epsilon', default=25.0, type=float,
+                   help='inlier threshold on HALF the frame-pixel reprojection distance (the reference\'s unit)')
+    p.add_argument('--ransac_iters', default=0, type=int,
+                   help='0: every pair of views; N > 0: N sampled pairs per joint (the reference draws 10)')
+    p.add_argument('--seed', default=0, type=int, help='seed of the sampled pairs')
+    args = p.parse_args(argv)
+    if not 0 <= args.ransac_iters <= MAX_HYPOTHESES:
+        p.error('--ransac_iters {}: 0 (every pair) to {}'.format(args.ransac_iters, MAX_HYPOTHESES))
+    if args.ransac_epsilon != args.ransac_epsilon:
+        p.error('--ransac_epsilon is NaN')
+    return args
 
 
 def parse_views(text):
@@ -75,11 +104,19 @@ def parse_views(text):
 
 def build_model(name):
     if name in NOT_BUILT:
-        raise ValueError('MODEL.NAME {!r} is not built in this project: tools/evaluate_3D.py evaluates {}'.format(
-            name, ' / '.join(MODELS)))
+        hint = ' (RANSAC is a lifting method here: --triangulation ransac)' if name == 'ransac' else ''
+        raise ValueError('MODEL.NAME {!r} is not built in this project: tools/evaluate_3D.py evaluates {}{}'.format(
+            name, ' / '.join(MODELS), hint))
     if name not in MODELS:
         raise ValueError('MODEL.NAME {!r}: tools/evaluate_3D.py evaluates {}'.format(name, ' / '.join(MODELS)))
     return MODELS[name]
+
+
+def check_lifting(args, config):
+    """--triangulation against the cfg: the reference's DIRECT_OPTIMIZATION refinement is not built"""
+    if args.triangulation == 'ransac' and config.MODEL.DIRECT_OPTIMIZATION:
+        raise ValueError('MODEL.DIRECT_OPTIMIZATION true is not built in this project: --triangulation ransac ends '
+                         'with the DLT over the inlier views; set MODEL.DIRECT_OPTIMIZATION false')
 
 
 def main(argv=None):
@@ -87,6 +124,7 @@ def main(argv=None):
     update_config(cfg, args)
     views = parse_views(args.views)
     get_pose_net = build_model(cfg.MODEL.NAME)
+    check_lifting(args, cfg)
     frames = mhp.frames_dir(cfg.DATA_DIR)
     if not os.path.isdir(frames):
         sys.exit('evaluate_3D: {} not found: the 3-D evaluation reads the MHP multi-view frames '
@@ -104,6 +142,10 @@ def main(argv=None):
     K, V = cfg.MODEL.NUM_JOINTS, len(views)
     acc = Eval3DAccumulator(K, cfg.MODEL.HEATMAP_SIZE[0])
     timed, t_total = 0, 0.0
+    ransac = args.triangulation == 'ransac'
+    shared_pairs = all_view_pairs(V).to(device) if ransac and args.ransac_iters == 0 else None
+    kept = torch.zeros(V, K, dtype=torch.float64, device=device)      # frames in which view v was kept for joint k
+    n_frames, rng = 0, random.Random(args.seed)
     with torch.no_grad():
         for i, ret in enumerate(loader):
             imgs = ret['imgs']                                         # (B*V, 3, H, W), slot b * V + v
@@ -111,16 +153,27 @@ def main(argv=None):
             intrinsic = ret['intrinsic_matrix'].to(device, non_blocking=True)
             extrinsic = ret['extrinsic_matrices'].to(device, non_blocking=True)
             hm_inverse = ret['hm_inverse'].to(device, non_blocking=True)
+            pairs = shared_pairs
+            if ransac and pairs is None:
+                # the host decides the hypotheses: one stream of draws over the whole evaluation, joint after joint
+                pairs = sample_view_pairs(B * K, V, args.ransac_iters, rng).to(device)
             torch.cuda.synchronize()
             t0 = time.time()
             hm = model(imgs)[0]      # (heatmaps, inter_feat[, temperature])
             pred = get_final_preds(hm, cfg.MODEL.HEATMAP_SOFTMAX)     # (B*V, K, 2) heat-map pixels
             proj = intrinsic[:, None] @ extrinsic                      # (B, V, 3, 4)
-            pose3d = triangulate_batch_of_points(proj, pred.view(B, V, K, 2), to_frame=hm_inverse)
+            if ransac:
+                pose3d, inl = triangulate_ransac_batch(proj, pred.view(B, V, K, 2), pairs, args.ransac_epsilon,
+                                                       to_frame=hm_inverse)
+            else:
+                pose3d = triangulate_batch_of_points(proj, pred.view(B, V, K, 2), to_frame=hm_inverse)
             torch.cuda.synchronize()
             if i >= 20 or i >= len(loader) // 2:
                 t_total += time.time() - t0
                 timed += B
+            if ransac:
+                kept += inl.sum(0).t()
+                n_frames += B
             acc.add(pred.cpu().numpy(), ret['pose2d'].numpy(), ret['visibility'].numpy(), ret['hm_inverse'].numpy(),
                     pose3d.cpu().numpy(), ret['pose3d'].numpy())
     out_dir = os.path.join(cfg.OUTPUT_DIR or 'output', 'eval3D_results_' + cfg.EXP_NAME)
@@ -131,6 +184,11 @@ def main(argv=None):
     print('3D pose EPE: {:.4f} mm'.format(np.nanmean(mse3d) if acc.n_valid else float('nan')))
     print('2D PCKAUC: {:.4f}'.format(auc(pck2d[0], pck2d[1])))
     print('3D PCKAUC: {:.4f}'.format(auc(pck3d[0], pck3d[1])))
+    if ransac:
+        share = (kept / max(n_frames, 1)).cpu().numpy()                # (V, K)
+        np.savetxt(os.path.join(out_dir, 'ransac_inliers.txt'), share)
+        print('RANSAC inlier views per joint: {:.3f} of {}; dropped per camera: {}'.format(
+            share.sum(0).mean(), V, ' '.join('cam{} {:.1%}'.format(c, 1.0 - s) for c, s in zip(views, share.mean(1)))))
     print('results in {}'.format(out_dir))
 
 

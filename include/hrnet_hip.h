@@ -579,6 +579,29 @@ int hrnet_triangulate(const float* pts, const double* to_frame, const double* pr
                       float* pts_frame, int B, int V, int K, hr_stream_t stream);
 
 /*
+ * RANSAC over the views, then the DLT of hrnet_triangulate over the chosen views (reference lib/utils/misc.py:178-240
+ * with direct_optimization off, as RANSACTriangulationNet.forward calls it). pts, to_frame, proj, pts_frame and
+ * B, V, K as in hrnet_triangulate; there are no weights.
+ *   pairs     int32 view-index pairs, the hypotheses, chosen by the host (the kernel draws nothing):
+ *             pairs_per_point == 0: [n_hyp,2], one table for all points; != 0: [B*K,n_hyp,2], point b*K + k
+ *   epsilon   inlier threshold on HALF the pixel distance in the frame between a view's point and the reprojection
+ *             of the two-view solution (the reference's `1 / 2 * sqrt(...)`, multiview.py:196): 25 means 50 px
+ *   X         [B,K,3] f32: the DLT over the final set, its views in ascending order
+ *   inliers   [B,K] int32: bit v is set when view v is in the final set
+ * Per point the hypotheses are taken in table order: a two-view DLT of (i, j), the candidate set {i, j} + {v : err_v <
+ * epsilon}, which replaces the current set only when it is strictly larger (the first largest set wins). A pair with
+ * i == j or an index outside 0..V-1 is skipped; with no usable pair (or n_hyp == 0) the set is every view. A group of
+ * lanes per point solves the hypotheses side by side; the result does not depend on the grouping. Every solve is the
+ * f64 Givens QR + Jacobi SVD of hrnet_triangulate, so epsilon = +inf reproduces hrnet_triangulate bit for bit.
+ * 2 <= V <= 8, 0 <= n_hyp <= 64, epsilon not NaN. A non-finite point (after to_frame) or projection matrix in ANY view
+ * of a point makes its X NaN, although the rule alone would drop such a view (its error is never below epsilon): as
+ * in hrnet_triangulate, a fault upstream is not hidden. The mask is then the one the rule gives.
+ */
+int hrnet_triangulate_ransac(const float* pts, const double* to_frame, const double* proj, const int* pairs, int n_hyp,
+                             int pairs_per_point, double epsilon, float* X, int* inliers, float* pts_frame, int B,
+                             int V, int K, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
