@@ -1,4 +1,4 @@
-// Heat-map loss, key-point decode, key-point loss and the Adam step: small HBM/latency-bound
+// Heat-map loss, key-point decode, key-point loss, hand-structure losses and the Adam step: small HBM/latency-bound
 // kernels on the NCHW f32 tensors of the module contract. One wavefront-friendly block per
 // (batch, joint) map; reductions by DPP/shuffle then LDS, in a fixed order.
 #include "common.h"
@@ -277,6 +277,210 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
   }
 }
 
+// ---- hand-structure regularisers (reference lib/core/loss.py:150-223 after lib/utils/transforms.py:146-175) ----
+// One thread owns one sample: its 21 joints, the 20 bones and the 15 cross products live in f64 registers (every index
+// below is a compile-time constant). Non-finite values are carried, never tested for: a zero scale makes the sample's
+// losses and gradients NaN/inf exactly as the reference's autograd does.
+constexpr int kHandJoints = 21;
+constexpr int kStructThreads = 256;
+
+// scale_pose2d: relative to the wrist, then divided by the wrist-to-joint-9 length (no epsilon); returns that length
+__device__ __forceinline__ double hand_scale(double (&x)[kHandJoints][2]) {
+  const double wx = x[0][0], wy = x[0][1];
+#pragma unroll
+  for (int j = 0; j < kHandJoints; ++j) {
+    x[j][0] -= wx;
+    x[j][1] -= wy;
+  }
+  const double ux = x[9][0] - x[0][0], uy = x[9][1] - x[0][1];
+  const double s = sqrt(ux * ux + uy * uy);
+#pragma unroll
+  for (int j = 0; j < kHandJoints; ++j) {
+    x[j][0] /= s;
+    x[j][1] /= s;
+  }
+  return s;
+}
+
+// g = d loss / d x (x the poses the loss saw) -> d loss / d pred, through scale_pose2d when `normalize`; f32 out
+__device__ __forceinline__ void hand_grad_store(double (&g)[kHandJoints][2], const double (&x)[kHandJoints][2],
+                                                double s, int normalize, float* __restrict__ out) {
+  if (normalize) {
+    // x = r / s: d/dr = g / s, d/ds = -sum(g . x) / s; s = |r9 - r0| with torch's norm backward (0 at the origin)
+    double gs = 0.0;
+#pragma unroll
+    for (int j = 0; j < kHandJoints; ++j) {
+      gs += g[j][0] * x[j][0] + g[j][1] * x[j][1];
+      g[j][0] /= s;
+      g[j][1] /= s;
+    }
+    gs = -gs / s;
+    const double ux = x[9][0] - x[0][0], uy = x[9][1] - x[0][1];      // (r9 - r0) / s, a unit vector
+    const double nx = s == 0.0 ? 0.0 : ux, ny = s == 0.0 ? 0.0 : uy;
+    g[9][0] += gs * nx;
+    g[9][1] += gs * ny;
+    g[0][0] -= gs * nx;
+    g[0][1] -= gs * ny;
+    // r_j = p_j - p_0 for every j, the wrist included
+    double sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int j = 0; j < kHandJoints; ++j) {
+      sx += g[j][0];
+      sy += g[j][1];
+    }
+    g[0][0] -= sx;
+    g[0][1] -= sy;
+  }
+#pragma unroll
+  for (int j = 0; j < kHandJoints; ++j) {
+    out[2 * j] = (float)g[j][0];
+    out[2 * j + 1] = (float)g[j][1];
+  }
+}
+
+__device__ __forceinline__ void hand_load(const float* __restrict__ p, double (&x)[kHandJoints][2]) {
+#pragma unroll
+  for (int j = 0; j < kHandJoints; ++j) {
+    x[j][0] = (double)p[2 * j];
+    x[j][1] = (double)p[2 * j + 1];
+  }
+}
+
+// terms: bit 0 bone-length loss, bit 1 joint-angle loss. A single workgroup walks the batch 256 samples at a time and
+// thread 0 adds the per-sample terms in sample order, so the sums do not depend on anything but the input.
+__global__ __launch_bounds__(kStructThreads) void structure_loss_kernel(const float* __restrict__ pred,
+                                                                        const float* __restrict__ gt,
+                                                                        float* __restrict__ loss_bone,
+                                                                        float* __restrict__ loss_angle,
+                                                                        float* __restrict__ dbone,
+                                                                        float* __restrict__ dangle, int B,
+                                                                        int normalize, int terms) {
+  __shared__ double part[2][kStructThreads];
+  double sum_bone = 0.0, sum_angle = 0.0;            // thread 0 only
+  for (int base = 0; base < B; base += kStructThreads) {
+    const int b = base + (int)threadIdx.x;
+    double lb = 0.0, la = 0.0;
+    if (b < B) {
+      double x[kHandJoints][2], g[kHandJoints][2];
+      hand_load(pred + (size_t)b * kHandJoints * 2, x);
+      const double s = normalize ? hand_scale(x) : 1.0;
+      if (terms & 1) {
+        // bone j = x[j] - x[j-1] for EVERY j = 1..20 (the reference's finger-base branch is never taken)
+        double lg[kHandJoints];
+        {
+          double y[kHandJoints][2];
+          hand_load(gt + (size_t)b * kHandJoints * 2, y);
+          if (normalize) hand_scale(y);
+#pragma unroll
+          for (int j = 1; j < kHandJoints; ++j) {
+            const double dx = y[j][0] - y[j - 1][0], dy = y[j][1] - y[j - 1][1];
+            lg[j] = sqrt(dx * dx + dy * dy);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < kHandJoints; ++j) g[j][0] = g[j][1] = 0.0;
+#pragma unroll
+        for (int j = 1; j < kHandJoints; ++j) {
+          const double dx = x[j][0] - x[j - 1][0], dy = x[j][1] - x[j - 1][1];
+          const double lp = sqrt(dx * dx + dy * dy);
+          const double e = lg[j] - lp;
+          lb += e * e;
+          // d (e^2 / 20) / d lp = -2 e / 20; torch.norm backward: d / lp, 0 for a zero-length bone
+          const double c = -2.0 * e / 20.0;
+          const double nx = lp == 0.0 ? 0.0 : dx / lp, ny = lp == 0.0 ? 0.0 : dy / lp;
+          g[j][0] += c * nx;
+          g[j][1] += c * ny;
+          g[j - 1][0] -= c * nx;
+          g[j - 1][1] -= c * ny;
+        }
+        if (dbone) hand_grad_store(g, x, s, normalize, dbone + (size_t)b * kHandJoints * 2);
+      }
+      if (terms & 2) {
+#pragma unroll
+        for (int j = 0; j < kHandJoints; ++j) g[j][0] = g[j][1] = 0.0;
+#pragma unroll
+        for (int f = 0; f < 5; ++f) {
+          // finger f = joints 4f..4f+4; z = 0, so every cross product is its z component
+          double bx[5], by[5];
+#pragma unroll
+          for (int i = 1; i <= 4; ++i) {
+            bx[i] = x[4 * f + i][0] - x[4 * f + i - 1][0];
+            by[i] = x[4 * f + i][1] - x[4 * f + i - 1][1];
+          }
+          const double c43 = bx[4] * by[3] - by[4] * bx[3];
+          const double c32 = bx[3] * by[2] - by[3] * bx[2];
+          const double c21 = bx[2] * by[1] - by[2] * bx[1];
+          const double d1 = c43 * c32, d2 = c21 * c32;
+          // Rule 1 (coplanarity) as the reference evaluates it on z = 0: exactly zero with zero gradient for finite
+          // poses, NaN for non-finite ones - it is what makes a zero-scale sample's angle loss NaN
+          la += ((by[2] * 0.0 - 0.0 * by[1]) * bx[4] + (0.0 * bx[1] - bx[2] * 0.0) * by[4] + c21 * 0.0) +
+                ((by[3] * 0.0 - 0.0 * by[2]) * bx[4] + (0.0 * bx[2] - bx[3] * 0.0) * by[4] + c32 * 0.0);
+          double g43 = 0.0, g32 = 0.0, g21 = 0.0;
+          if (d1 < 0.0) {
+            la += d1 * d1;
+            g43 += 2.0 * d1 * c32;
+            g32 += 2.0 * d1 * c43;
+          }
+          if (d2 < 0.0) {
+            la += d2 * d2;
+            g21 += 2.0 * d2 * c32;
+            g32 += 2.0 * d2 * c21;
+          }
+          // c = u x v = u.x v.y - u.y v.x: dc/du = (v.y, -v.x), dc/dv = (-u.y, u.x)
+          double gbx[5], gby[5];
+          gbx[4] = g43 * by[3];
+          gby[4] = -g43 * bx[3];
+          gbx[3] = -g43 * by[4] + g32 * by[2];
+          gby[3] = g43 * bx[4] - g32 * bx[2];
+          gbx[2] = -g32 * by[3] + g21 * by[1];
+          gby[2] = g32 * bx[3] - g21 * bx[1];
+          gbx[1] = -g21 * by[2];
+          gby[1] = g21 * bx[2];
+#pragma unroll
+          for (int i = 1; i <= 4; ++i) {
+            g[4 * f + i][0] += gbx[i];
+            g[4 * f + i][1] += gby[i];
+            g[4 * f + i - 1][0] -= gbx[i];
+            g[4 * f + i - 1][1] -= gby[i];
+          }
+        }
+        if (dangle) hand_grad_store(g, x, s, normalize, dangle + (size_t)b * kHandJoints * 2);
+      }
+    }
+    part[0][threadIdx.x] = lb;
+    part[1][threadIdx.x] = la;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int n = min(kStructThreads, B - base);
+      for (int i = 0; i < n; ++i) {
+        sum_bone += part[0][i];
+        sum_angle += part[1][i];
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (terms & 1) loss_bone[0] = (float)(sum_bone / 20.0);
+    if (terms & 2) loss_angle[0] = (float)sum_angle;
+  }
+}
+
+// dpred = g_bone * dbone + g_angle * dangle; a NULL upstream gradient drops its term
+__global__ __launch_bounds__(256) void structure_loss_bwd_kernel(const float* __restrict__ dbone,
+                                                                 const float* __restrict__ dangle,
+                                                                 const float* __restrict__ g_bone,
+                                                                 const float* __restrict__ g_angle,
+                                                                 float* __restrict__ dpred, long long n) {
+  const float gb = g_bone ? g_bone[0] : 0.f, ga = g_angle ? g_angle[0] : 0.f;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    float v = 0.f;
+    if (g_bone) v = gb * dbone[i];
+    if (g_angle) v = g_bone ? fmaf(ga, dangle[i], v) : ga * dangle[i];
+    dpred[i] = v;
+  }
+}
+
 }  // namespace
 
 extern "C" int hrnet_heatmap_loss_fwd(const float* pred, const float* gt, float* partial, float* loss,
@@ -372,6 +576,33 @@ extern "C" int hrnet_joints_loss_bwd(const float* pred, const float* gt, const f
   hipLaunchKernelGGL(joints_loss_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, gt, vis,
                      gout, dpred, B, K);
   return hr_check_launch("joints_loss_bwd");
+}
+
+extern "C" int hrnet_structure_loss(const float* pred, const float* gt, float* loss_bone, float* loss_angle,
+                                    float* dbone_dpred, float* dangle_dpred, int B, int K, int normalize, int terms,
+                                    hr_stream_t stream) {
+  HR_REQUIRE(pred && B > 0, "structure_loss: args");
+  HR_REQUIRE(K == kHandJoints, "structure_loss: K must be 21 (the hand skeleton of the reference's losses)");
+  HR_REQUIRE(terms >= 1 && terms <= 3, "structure_loss: terms is a mask of 1 (bone length) and 2 (joint angle)");
+  HR_REQUIRE(!(terms & 1) || (gt && loss_bone), "structure_loss: the bone-length term needs gt and loss_bone");
+  HR_REQUIRE(!(terms & 2) || loss_angle, "structure_loss: the joint-angle term needs loss_angle");
+  hipLaunchKernelGGL(structure_loss_kernel, dim3(1), dim3(kStructThreads), 0, (hipStream_t)stream, pred, gt,
+                     loss_bone, loss_angle, (terms & 1) ? dbone_dpred : nullptr, (terms & 2) ? dangle_dpred : nullptr,
+                     B, normalize ? 1 : 0, terms);
+  return hr_check_launch("structure_loss");
+}
+
+extern "C" int hrnet_structure_loss_bwd(const float* dbone_dpred, const float* dangle_dpred, const float* g_bone,
+                                        const float* g_angle, float* dpred, int B, int K, hr_stream_t stream) {
+  HR_REQUIRE(dpred && B > 0 && K == kHandJoints, "structure_loss_bwd: args");
+  HR_REQUIRE((g_bone || g_angle) && (!g_bone || dbone_dpred) && (!g_angle || dangle_dpred),
+             "structure_loss_bwd: an upstream gradient needs its unit gradient");
+  const long long n = (long long)B * K * 2;
+  long long grid = (n + 255) / 256;
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(structure_loss_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
+                     dbone_dpred, dangle_dpred, g_bone, g_angle, dpred, n);
+  return hr_check_launch("structure_loss_bwd");
 }
 
 extern "C" int hrnet_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

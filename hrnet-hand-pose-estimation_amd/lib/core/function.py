@@ -11,6 +11,11 @@ maps). The reference's validate skips that name (function.py:800), so validating
 TEST_DATASET did nothing there; here it computes the validation losses. 'MHP' (dataset/mhp.py) is accepted
 the same way.
 
+LOSS.WITH_BONE_LOSS / LOSS.WITH_JOINTANGLE_LOSS (reference function.py:1352-1373, messages :142-151, :760-766,
+:786-788): `computeLosses` evaluates both terms on the scale_pose2d-normalised key points in one launch
+(core.loss.structure_losses). Both loops log the validation spelling `JointAngleLoss` (the reference's training loop
+writes `JointangleLoss`).
+
 `debug`: the reference hard-codes a module-level `debug = True` that stops every epoch after 5
 iterations (function.py:22,193,812). Here it defaults to False; set `core.function.debug = True`
 to reproduce that behaviour.
@@ -19,6 +24,7 @@ import time
 
 import torch
 
+from core.loss import TERM_ANGLE, TERM_BONE, structure_losses
 from utils.heatmap_decoding import get_final_preds
 
 debug = False
@@ -27,7 +33,9 @@ GENERIC_DATASETS = ('HandGraph_kpt', 'RHD_kpt', 'FreiHand_kpt', 'MHP_kpt', 'MHP_
 VALID_DATASETS = GENERIC_DATASETS + ('RHD', 'MHP')
 
 _LOSS_NAMES = (('heatmap_loss', 'WITH_HEATMAP_LOSS', 'HeatmapLoss', 'heatmap_loss'),
-               ('pose2d_loss', 'WITH_POSE2D_LOSS', 'Pose2DLoss', 'pose2d_loss'))
+               ('pose2d_loss', 'WITH_POSE2D_LOSS', 'Pose2DLoss', 'pose2d_loss'),
+               ('bone_loss', 'WITH_BONE_LOSS', 'BoneLoss', 'bone_loss'),
+               ('jointangle_loss', 'WITH_JOINTANGLE_LOSS', 'JointAngleLoss', 'jointangle_loss'))
 
 
 class AverageMeter(object):
@@ -42,14 +50,11 @@ class AverageMeter(object):
         # step here (bench.py --pose2d-loss). The attributes below read the same numbers, syncing only when they are
         # read (every PRINT_FREQ steps and at the end of an epoch).
         self._sums = {'total_loss': 0.}
-        if L.WITH_HEATMAP_LOSS:
-            self._sums['heatmap_loss'] = 0.
-        if L.WITH_POSE2D_LOSS:
-            self._sums['pose2d_loss'] = 0.
+        for key, flag, _label, _attr in _LOSS_NAMES:
+            if getattr(L, flag):
+                self._sums[key] = 0.
         self.pose3d_loss = 0. if L.WITH_POSE3D_LOSS else None
         self.time_consistency_loss = 0. if L.WITH_TIME_CONSISTENCY_LOSS else None
-        self.bone_loss = 0. if L.WITH_BONE_LOSS else None
-        self.jointangle_loss = 0. if L.WITH_JOINTANGLE_LOSS else None
         self.n = 0
 
     def _read(self, key):
@@ -59,15 +64,17 @@ class AverageMeter(object):
     total_loss = property(lambda self: self._read('total_loss'))
     heatmap_loss = property(lambda self: self._read('heatmap_loss'))
     pose2d_loss = property(lambda self: self._read('pose2d_loss'))
+    bone_loss = property(lambda self: self._read('bone_loss'))
+    jointangle_loss = property(lambda self: self._read('jointangle_loss'))
 
     def computeAvgLosses(self):
         n = max(self.n, 1)
         self.avg_total_loss = self.total_loss / n
         out = {'total_loss': self.avg_total_loss}
-        if self.config.LOSS.WITH_HEATMAP_LOSS:
-            self.avg_heatmap_loss = out['heatmap_loss'] = self.heatmap_loss / n
-        if self.config.LOSS.WITH_POSE2D_LOSS:
-            self.avg_pose2d_loss = out['pose2d_loss'] = self.pose2d_loss / n
+        for key, flag, _label, attr in _LOSS_NAMES:
+            if getattr(self.config.LOSS, flag):
+                out[key] = self._read(key) / n
+                setattr(self, 'avg_' + attr, out[key])
         return out
 
     def computeLosses(self, heatmaps_pred=None, heatmaps_gt=None, pose2d_pred=None, pose2d_gt=None,
@@ -86,9 +93,20 @@ class AverageMeter(object):
             self._sums['pose2d_loss'] = self._sums['pose2d_loss'] + l.detach()
             total = total + self.config.LOSS.POSE2D_LOSS_FACTOR * l
             out['pose2d_loss'] = l
-        for other in ('pose3d_loss', 'bone_loss', 'jointangle_loss'):
-            if other in names:
-                raise NotImplementedError('{} belongs to model families outside the HRNet 2-D hot path'.format(other))
+        terms = (TERM_BONE if 'bone_loss' in names else 0) | (TERM_ANGLE if 'jointangle_loss' in names else 0)
+        if terms:
+            # both terms after scale_pose2d of both poses, one launch (reference function.py:1352-1373 calls the two
+            # criterion modules on the scaled poses; here the criterion entries select the terms)
+            bone, angle = structure_losses(pose2d_pred[:, :, 0:2], pose2d_gt if terms & TERM_BONE else None,
+                                           terms=terms, normalize=True)
+            for key, l, factor in (('bone_loss', bone, self.config.LOSS.BONE_LOSS_FACTOR),
+                                   ('jointangle_loss', angle, self.config.LOSS.JOINTANGLE_LOSS_FACTOR)):
+                if l is not None:
+                    self._sums[key] = self._sums[key] + l.detach()
+                    total = total + factor * l
+                    out[key] = l
+        if 'pose3d_loss' in names:
+            raise NotImplementedError('pose3d_loss belongs to model families outside the HRNet 2-D hot path')
         self._sums['total_loss'] = self._sums['total_loss'] + total.detach()
         out['total_loss'] = total
         return out
@@ -107,8 +125,9 @@ def _forward_and_losses(config, ret, model, recorder, device):
     pose2d_pred = get_final_preds(heatmaps_pred, use_softmax=config.MODEL.HEATMAP_SOFTMAX)
     if config.LOSS.WITH_HEATMAP_LOSS:
         heatmaps_gt = _to_device(heatmaps_gt, device)
-    if config.LOSS.WITH_POSE2D_LOSS:
+    if config.LOSS.WITH_POSE2D_LOSS or config.LOSS.WITH_BONE_LOSS:
         pose2d_gt = _to_device(pose2d_gt, device)
+    if config.LOSS.WITH_POSE2D_LOSS:
         visibility = _to_device(visibility, device)
     visibility = visibility.reshape(visibility.shape[0], -1)     # B x K (the reference squeezes)
     return imgs, recorder.computeLosses(heatmaps_pred, heatmaps_gt, pose2d_pred, pose2d_gt, visibility=visibility)
@@ -212,9 +231,8 @@ def validate(config, args, master, val_loader_dict, model, criterion, output_dir
         steps = writer_dict['valid_global_steps']
         if master and writer is not None:
             writer.add_scalar('val_loss/total_loss', recorder.avg_total_loss, steps)
-            if config.LOSS.WITH_HEATMAP_LOSS:
-                writer.add_scalar('val_loss/heatmap_loss', recorder.avg_heatmap_loss, steps)
-            if config.LOSS.WITH_POSE2D_LOSS:
-                writer.add_scalar('val_loss/pose2d_loss', recorder.avg_pose2d_loss, steps)
+            for key, flag, _label, attr in _LOSS_NAMES:
+                if getattr(config.LOSS, flag):
+                    writer.add_scalar('val_loss/' + key, getattr(recorder, 'avg_' + attr), steps)
         writer_dict['valid_global_steps'] = steps + 1
     return recorder

@@ -152,6 +152,8 @@ _SIGS = {
                                 [_c_vp],
     'hrnet_joints_loss_fwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
+    'hrnet_structure_loss': [_c_vp] * 6 + [_c_int] * 4 + [_c_vp],
+    'hrnet_structure_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_adam_step': [_c_vp] * 4 + [_c_i64] + [_c_float] * 5 + [_c_int, _c_float, _c_vp],
     'hrnet_deform_conv_forward': [_c_vp] * 5 + [_c_int] * 15 + [_c_vp],
     'hrnet_deform_conv_wgrad_blocks': [_c_int] * 3,

@@ -22,7 +22,7 @@ import torch
 
 from config import cfg, update_config
 from core.function import train, validate
-from core.loss import HeatmapLoss, JointsMSELoss
+from core.loss import BoneLengthLoss, HeatmapLoss, JointAngleLoss, JointsMSELoss
 from dataset.build import make_dataloader
 from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax  # noqa: F401  (dispatched by name below)
 from utils.utils import create_logger, get_optimizer, save_checkpoint
@@ -40,6 +40,23 @@ def parse_args():
     p.add_argument('--batches-per-epoch', default=None, type=int,
                    help='batches per training epoch (synthetic loader: default 8; a real dataset: every batch)')
     return p.parse_args()
+
+
+def build_criterion(cfg, device=None):
+    """the loss modules the LOSS.WITH_* flags ask for, keyed as core.function.AverageMeter expects them (reference
+    tools/train.py:256-265); the modules hold no parameters, so `device` None leaves them where they are. The 'bone_loss' / 'jointangle_loss'
+    entries SELECT the terms that AverageMeter.computeLosses evaluates in one fused launch (core.loss.structure_losses);
+    the module objects under those two keys are not called by the loop - they are there for direct use"""
+    criterion = {}
+    if cfg.LOSS.WITH_HEATMAP_LOSS:
+        criterion['heatmap_loss'] = HeatmapLoss()
+    if cfg.LOSS.WITH_POSE2D_LOSS:
+        criterion['pose2d_loss'] = JointsMSELoss()
+    if cfg.LOSS.WITH_BONE_LOSS:
+        criterion['bone_loss'] = BoneLengthLoss()
+    if cfg.LOSS.WITH_JOINTANGLE_LOSS:
+        criterion['jointangle_loss'] = JointAngleLoss()
+    return criterion if device is None else {k: m.to(device) for k, m in criterion.items()}
 
 
 def main():
@@ -73,11 +90,7 @@ def main():
         from hipnet.optim import GradSync
         sync = GradSync(model)        # broadcasts rank 0's parameters / buffers, as DDP's constructor does
 
-    criterion = {}
-    if cfg.LOSS.WITH_HEATMAP_LOSS:
-        criterion['heatmap_loss'] = HeatmapLoss().to(device)
-    if cfg.LOSS.WITH_POSE2D_LOSS:
-        criterion['pose2d_loss'] = JointsMSELoss().to(device)
+    criterion = build_criterion(cfg, device)
     optimizer = get_optimizer(cfg, model)
     if sync is not None:
         sync.attach(optimizer)        # 1/world: folded into FlatAdam, applied in finish() for torch optimizers

@@ -621,6 +621,31 @@ int hrnet_joints_loss_fwd(const float* pred, const float* gt, const float* vis, 
 int hrnet_joints_loss_bwd(const float* pred, const float* gt, const float* vis, const float* gout,
                           float* dpred, int B, int K, hr_stream_t stream);
 
+/*
+ * Hand-structure regularisers of the 2-D training step: BoneLengthLoss and JointAngleLoss (lib/core/loss.py:150-223)
+ * on 2-D poses, optionally after scale_pose2d (lib/utils/transforms.py:146-175) of both poses. ONE launch for any B.
+ *   pred, gt [B,21,2] f32 (gt may be NULL without the bone term); K must be 21;
+ *   normalize != 0: r = p - p[0], then r / ||r[9] - r[0]|| per sample, no epsilon;
+ *   terms: bit 0 bone length, bit 1 joint angle; outputs of a term that is off are not touched.
+ *   loss_bone[0]  = sum over batch and j = 1..20 of (|gt[j]-gt[j-1]| - |pred[j]-pred[j-1]|)^2 / 20 (every j: the
+ *                   bones 5-4, 9-8, 13-12, 17-16 included, as the reference computes them; a sum over the batch);
+ *   loss_angle[0] = sum over batch and fingers f = 0..4 (joints 4f..4f+4, bone_i = x[4f+i] - x[4f+i-1]) of d^2 for
+ *                   each d < 0 of d1 = (b4 x b3)(b3 x b2), d2 = (b2 x b1)(b3 x b2), u x v = u.x v.y - u.y v.x;
+ *                   the coplanarity rule is exactly zero on z = 0 and enters only as the IEEE value the reference
+ *                   gives it (0 for finite poses, NaN for non-finite ones);
+ *   dbone_dpred, dangle_dpred [B,21,2] f32 or NULL: d loss / d pred (the UNSCALED pred, through the normalisation).
+ * f32 in and out, f64 inside; the batch sum runs in sample order, so a call is bit-reproducible. A zero-length
+ * predicted or ground-truth bone has no gradient (torch.norm backward); a zero scale makes both losses and that
+ * sample's gradients non-finite, as in the reference - they are returned, nothing traps.
+ * hrnet_structure_loss_bwd: dpred = *g_bone * dbone_dpred + *g_angle * dangle_dpred, one launch; g_* are device
+ * scalars, a NULL one drops its term (at least one is given).
+ */
+int hrnet_structure_loss(const float* pred, const float* gt, float* loss_bone, float* loss_angle,
+                         float* dbone_dpred, float* dangle_dpred, int B, int K, int normalize, int terms,
+                         hr_stream_t stream);
+int hrnet_structure_loss_bwd(const float* dbone_dpred, const float* dangle_dpred, const float* g_bone,
+                             const float* g_angle, float* dpred, int B, int K, hr_stream_t stream);
+
 /* Adam step over a flat f32 parameter buffer (torch.optim.Adam semantics incl. L2 weight
  * decay added to the gradient; lib/utils/utils.py:81-85, lib/core/function.py:101-106). */
 int hrnet_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
