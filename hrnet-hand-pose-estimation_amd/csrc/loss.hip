@@ -260,6 +260,44 @@ __global__ __launch_bounds__(256) void joints_loss_bwd_kernel(const float* pred,
   }
 }
 
+// Joints3DMSELoss (reference lib/core/loss.py:137-148): sum over batch and joints of ||gt - pred||_2, over K. One
+// workgroup; f64 inside; every thread adds its points in index order and thread 0 adds the 256 partial sums in thread
+// order, so the result depends on nothing but the input.
+__global__ __launch_bounds__(256) void joints3d_loss_fwd_kernel(const float* __restrict__ pred,
+                                                                const float* __restrict__ gt,
+                                                                float* __restrict__ loss, int B, int K) {
+  __shared__ double part[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < B * K; i += 256) {
+    const double dx = (double)gt[3 * i] - (double)pred[3 * i], dy = (double)gt[3 * i + 1] - (double)pred[3 * i + 1],
+                 dz = (double)gt[3 * i + 2] - (double)pred[3 * i + 2];
+    s += sqrt(dx * dx + dy * dy + dz * dz);
+  }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = 0.0;
+    for (int i = 0; i < 256; ++i) total += part[i];
+    loss[0] = (float)(total / (double)K);
+  }
+}
+
+__global__ __launch_bounds__(256) void joints3d_loss_bwd_kernel(const float* __restrict__ pred,
+                                                                const float* __restrict__ gt,
+                                                                const float* __restrict__ gout,
+                                                                float* __restrict__ dpred, int n, int K) {
+  const double g = (double)gout[0] / (double)K;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const double dx = (double)pred[3 * i] - (double)gt[3 * i], dy = (double)pred[3 * i + 1] - (double)gt[3 * i + 1],
+                 dz = (double)pred[3 * i + 2] - (double)gt[3 * i + 2];
+    const double nrm = sqrt(dx * dx + dy * dy + dz * dz);
+    // torch.norm backward: x / ||x||, 0 at the origin
+    dpred[3 * i] = nrm == 0.0 ? 0.f : (float)(g * dx / nrm);
+    dpred[3 * i + 1] = nrm == 0.0 ? 0.f : (float)(g * dy / nrm);
+    dpred[3 * i + 2] = nrm == 0.0 ? 0.f : (float)(g * dz / nrm);
+  }
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v,
                                                    long long n, float lr, float b1, float b2, float eps,
                                                    float wd, float bc1, float bc2_sqrt, float gscale) {
@@ -576,6 +614,25 @@ extern "C" int hrnet_joints_loss_bwd(const float* pred, const float* gt, const f
   hipLaunchKernelGGL(joints_loss_bwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, gt, vis,
                      gout, dpred, B, K);
   return hr_check_launch("joints_loss_bwd");
+}
+
+extern "C" int hrnet_joints3d_loss_fwd(const float* pred, const float* gt, float* loss, int B, int K,
+                                       hr_stream_t stream) {
+  HR_REQUIRE(pred && gt && loss && B > 0 && K > 0 && (long long)B * K <= (1LL << 28), "joints3d_loss_fwd: args");
+  hipLaunchKernelGGL(joints3d_loss_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, gt, loss, B, K);
+  return hr_check_launch("joints3d_loss_fwd");
+}
+
+extern "C" int hrnet_joints3d_loss_bwd(const float* pred, const float* gt, const float* gout, float* dpred, int B,
+                                       int K, hr_stream_t stream) {
+  HR_REQUIRE(pred && gt && gout && dpred && B > 0 && K > 0 && (long long)B * K <= (1LL << 28),
+             "joints3d_loss_bwd: args");
+  const int n = B * K;
+  int grid = (n + 255) / 256;
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(joints3d_loss_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, pred, gt,
+                     gout, dpred, n, K);
+  return hr_check_launch("joints3d_loss_bwd");
 }
 
 extern "C" int hrnet_structure_loss(const float* pred, const float* gt, float* loss_bone, float* loss_angle,

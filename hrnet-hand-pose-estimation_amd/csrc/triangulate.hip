@@ -17,6 +17,10 @@
 // set that agrees with a two-view solution, see triangulate_ransac_kernel - and ends with the same DLT over that set.
 // Both kernels share the device functions below, called in the same order, so that where the sets coincide the two
 // results are the same bits.
+//
+// hrnet_triangulate_bwd is the gradient of the all-view DLT with respect to the points and the weights, for the 3-D
+// training loss (see triangulate_bwd_kernel). It recomputes the forward's SVD from the same inputs with the same
+// device functions and needs nothing saved.
 #include "common.h"
 
 namespace {
@@ -143,6 +147,28 @@ __device__ __forceinline__ void tri_null_vector(double (&R)[4][4], double (&h)[4
   }
 }
 
+// The SVD of tri_null_vector, step for step, for the backward, which needs all of it: R becomes R V (orthogonal
+// columns), Vm holds the right singular vectors and n[j] the SQUARED singular value of column j (the squared norm of
+// column j of R V); the columns are not sorted. It is a function of its own so that the forward kernels compile to the
+// code they had before the backward existed.
+__device__ __forceinline__ void tri_svd(double (&R)[4][4], double (&Vm)[4][4], double (&n)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) Vm[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kTriSweeps; ++sweep) {
+    bool rotated = tri_jacobi<0, 1>(R, Vm);
+    rotated |= tri_jacobi<0, 2>(R, Vm);
+    rotated |= tri_jacobi<0, 3>(R, Vm);
+    rotated |= tri_jacobi<1, 2>(R, Vm);
+    rotated |= tri_jacobi<1, 3>(R, Vm);
+    rotated |= tri_jacobi<2, 3>(R, Vm);
+    if (!rotated) break;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) n[j] = R[0][j] * R[0][j] + R[1][j] * R[1][j] + R[2][j] * R[2][j] + R[3][j] * R[3][j];
+}
+
 __global__ __launch_bounds__(kTriThreads) void triangulate_kernel(const float* __restrict__ pts,
                                                                   const double* __restrict__ to_frame,
                                                                   const double* __restrict__ proj,
@@ -180,6 +206,108 @@ __global__ __launch_bounds__(kTriThreads) void triangulate_kernel(const float* _
   out[0] = (float)(h[0] / h[3]);
   out[1] = (float)(h[1] / h[3]);
   out[2] = (float)(h[2] / h[3]);
+}
+
+// Backward of triangulate_kernel, one thread per point, for the 3-D training loss (the reference back-propagates
+// through torch.svd, lib/models/triangulation_model_utils/multiview.py:164). Nothing is saved by the forward: R and its
+// Jacobi SVD are recomputed from the inputs with the forward's device functions in the forward's order, so h is the
+// forward's h, and the SVD already holds what the derivative needs - all four right singular vectors v_j (columns of
+// Vm) and squared singular values n_j. With m the forward's column (h = v_m) and g = dL/dX:
+//   g^ = dL/dh = [g / h3, -(g . h[0:3]) / h3^2]
+//   z  = -sum_{j != m} v_j (v_j . g^) / (n_j - n_m)            (first-order perturbation of a singular vector)
+//   dL/dA = (A z) h^T + (A h) z^T; row 2v of A is c a0 with a0 = u P[2] - P[0] (a1 = w P[2] - P[1] for row 2v+1), so
+//   dL/du = c^2 ((a0 . z)(h . P[2]) + (a0 . h)(z . P[2])), dL/dw likewise with a1,
+//   dL/dc = 2 c ((a0 . z)(a0 . h) + (a1 . z)(a1 . h)),
+// and (dL/du, dL/dw) goes back through the 2 x 2 part of to_frame to the given points. A^T A is never formed. The sign
+// of h cancels. A view of weight 0 gets exact zeros (c^2 and c are factors). A point with fewer than two weighted views
+// gets NaN in every view, as its X is NaN; a non-finite input makes the point's gradients NaN through the arithmetic.
+// A vanishing n_j - n_m gives what the formula gives (huge or non-finite), as torch.svd's backward does. The index m
+// is only compared against compile-time column numbers, so Vm and n stay in registers.
+__global__ __launch_bounds__(kTriThreads) void triangulate_bwd_kernel(
+    const float* __restrict__ pts, const double* __restrict__ to_frame, const double* __restrict__ proj,
+    const float* __restrict__ conf, const float* __restrict__ gX, float* __restrict__ dpts, float* __restrict__ dconf,
+    int B, int V, int K) {
+  const long long t = (long long)blockIdx.x * kTriThreads + threadIdx.x;
+  if (t >= (long long)B * K) return;
+  const long long b = t / K, k = t - b * K;
+  double R[4][4];
+  tri_zero(R);
+  int weighted = 0;
+  for (int v = 0; v < V; ++v) {
+    const long long slot = b * V + v;
+    const long long pi = slot * K + k;
+    double u, w;
+    tri_load_point(pts, to_frame, slot, pi, u, w);
+    const double c = conf ? (double)conf[pi] : 1.0;
+    if (c != 0.0) ++weighted;
+    tri_add_view(R, proj + 12 * slot, u, w, c);
+  }
+  if (weighted < 2) {
+    const float nan = __builtin_nanf("");
+    for (int v = 0; v < V; ++v) {
+      const long long pi = (b * V + v) * K + k;
+      dpts[2 * pi] = nan;
+      dpts[2 * pi + 1] = nan;
+      if (dconf) dconf[pi] = nan;
+    }
+    return;
+  }
+  double Vm[4][4], n[4];
+  tri_svd(R, Vm, n);
+  // the forward's choice: the first column of smallest norm
+  double best = n[0];
+  int m = 0;
+  double h[4] = {Vm[0][0], Vm[1][0], Vm[2][0], Vm[3][0]};
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    if (n[j] < best) {
+      best = n[j];
+      m = j;
+      h[0] = Vm[0][j];
+      h[1] = Vm[1][j];
+      h[2] = Vm[2][j];
+      h[3] = Vm[3][j];
+    }
+  }
+  const double g0 = (double)gX[3 * t], g1 = (double)gX[3 * t + 1], g2 = (double)gX[3 * t + 2];
+  const double gh[4] = {g0 / h[3], g1 / h[3], g2 / h[3], -(g0 * h[0] + g1 * h[1] + g2 * h[2]) / (h[3] * h[3])};
+  double z[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double dot = Vm[0][j] * gh[0] + Vm[1][j] * gh[1] + Vm[2][j] * gh[2] + Vm[3][j] * gh[3];
+    const double wgt = j == m ? 0.0 : -dot / (n[j] - best);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) z[i] += wgt * Vm[i][j];
+  }
+  for (int v = 0; v < V; ++v) {
+    const long long slot = b * V + v;
+    const long long pi = slot * K + k;
+    double u, w;
+    tri_load_point(pts, to_frame, slot, pi, u, w);
+    const double c = conf ? (double)conf[pi] : 1.0;
+    const double* P = proj + 12 * slot;
+    double a0z = 0.0, a0h = 0.0, a1z = 0.0, a1h = 0.0, p2z = 0.0, p2h = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double a0 = u * P[8 + j] - P[j], a1 = w * P[8 + j] - P[4 + j];
+      a0z += a0 * z[j];
+      a0h += a0 * h[j];
+      a1z += a1 * z[j];
+      a1h += a1 * h[j];
+      p2z += P[8 + j] * z[j];
+      p2h += P[8 + j] * h[j];
+    }
+    const double du = c * c * (a0z * p2h + a0h * p2z), dw = c * c * (a1z * p2h + a1h * p2z);
+    double dx = du, dy = dw;
+    if (to_frame) {
+      const double* mt = to_frame + 6 * slot;
+      dx = mt[0] * du + mt[3] * dw;
+      dy = mt[1] * du + mt[4] * dw;
+    }
+    dpts[2 * pi] = (float)dx;
+    dpts[2 * pi + 1] = (float)dy;
+    if (dconf) dconf[pi] = (float)(2.0 * c * (a0z * a0h + a1z * a1h));
+  }
 }
 
 // RANSAC over the views (reference lib/utils/misc.py:178-240 with direct_optimization off). A group of kRansacGroup
@@ -281,6 +409,20 @@ extern "C" int hrnet_triangulate(const float* pts, const double* to_frame, const
   hipLaunchKernelGGL(triangulate_kernel, dim3(blocks), dim3(kTriThreads), 0, (hipStream_t)stream, pts, to_frame, proj,
                      conf, X, pts_frame, B, V, K);
   return hr_check_launch("triangulate");
+}
+
+extern "C" int hrnet_triangulate_bwd(const float* pts, const double* to_frame, const double* proj, const float* conf,
+                                     const float* gX, float* dpts, float* dconf, int B, int V, int K,
+                                     hr_stream_t stream) {
+  HR_REQUIRE(pts && proj && gX && dpts, "triangulate_bwd: null argument");
+  HR_REQUIRE(V >= 2 && V <= kTriMaxViews, "triangulate_bwd: V = %d views (2..%d)", V, kTriMaxViews);
+  HR_REQUIRE(B > 0 && K > 0 && (long long)B * V * K <= (1LL << 30), "triangulate_bwd: B = %d, V = %d, K = %d", B, V,
+             K);
+  const long long n = (long long)B * K;
+  const unsigned blocks = (unsigned)((n + kTriThreads - 1) / kTriThreads);
+  hipLaunchKernelGGL(triangulate_bwd_kernel, dim3(blocks), dim3(kTriThreads), 0, (hipStream_t)stream, pts, to_frame,
+                     proj, conf, gX, dpts, dconf, B, V, K);
+  return hr_check_launch("triangulate_bwd");
 }
 
 extern "C" int hrnet_triangulate_ransac(const float* pts, const double* to_frame, const double* proj, const int* pairs,

@@ -2,6 +2,8 @@
 
 HeatmapLoss    mean over (B,K) of the per-map sum of (pred-gt)^2 (mode 'l2') or |pred-gt| ('l1')
 JointsMSELoss  visibility-weighted mean L2 norm of key-point errors (despite its name)
+Joints3DMSELoss sum over batch and joints of the L2 norm of the 3-D error, over K (reference :137-148: a sum over the
+               batch); f64 inside, fixed summation order
 BoneLengthLoss sum over batch and j = 1..20 of (|gt[j]-gt[j-1]| - |pred[j]-pred[j-1]|)^2, over 20: a sum over the
                batch, and EVERY consecutive pair is a bone (5-4, 9-8, 13-12, 17-16 included - the reference's
                finger-base branch is never taken)
@@ -12,7 +14,8 @@ structure_losses  what the training loop calls: both terms after scale_pose2d (r
                leaves d bone / d pred and d angle / d pred when pred requires grad; backward is one launch that
                combines them with the upstream gradients, nothing is recomputed
 
-All are autograd Functions over the C ABI (hrnet_heatmap_loss_*, hrnet_joints_loss_*, hrnet_structure_loss*);
+All are autograd Functions over the C ABI (hrnet_heatmap_loss_*, hrnet_joints_loss_*, hrnet_joints3d_loss_*,
+hrnet_structure_loss*);
 inputs must be HIP tensors - there is no CPU path. The structure terms take B x 21 x 2 poses only: 3-D poses (a real
 z, the reference's other use of the two classes) are refused.
 
@@ -103,6 +106,37 @@ class JointsMSELoss(nn.Module):
         if visibility is not None:
             vis = _dev_f32(visibility.to(pred.device), 'JointsMSELoss').reshape(pred.shape[0], pred.shape[1]).detach()
         return _JointsLossFn.apply(pred, gt, vis)
+
+
+class _Joints3DLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt):
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        C.call('hrnet_joints3d_loss_fwd', pred.data_ptr(), gt.data_ptr(), loss.data_ptr(), pred.shape[0],
+               pred.shape[1], C.stream_ptr())
+        ctx.save_for_backward(pred, gt)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt = ctx.saved_tensors
+        dpred = torch.empty_like(pred)
+        g = gout.contiguous().float().reshape(1)
+        C.call('hrnet_joints3d_loss_bwd', pred.data_ptr(), gt.data_ptr(), g.data_ptr(), dpred.data_ptr(),
+               pred.shape[0], pred.shape[1], C.stream_ptr())
+        return dpred, None
+
+
+class Joints3DMSELoss(nn.Module):
+    """pose3d_pred, pose3d_gt: B x K x 3 -> sum_{b,k} ||gt - pred||_2 / K (a sum over the batch, as the reference)."""
+
+    def forward(self, pose3d_pred, pose3d_gt):
+        pred = _dev_f32(pose3d_pred, 'Joints3DMSELoss')
+        gt = _dev_f32(pose3d_gt, 'Joints3DMSELoss').detach()
+        if pred.dim() != 3 or pred.shape[2] != 3 or pred.shape != gt.shape:
+            raise ValueError('Joints3DMSELoss expects two B x K x 3 poses, got {} and {}'.format(
+                tuple(pred.shape), tuple(gt.shape)))
+        return _Joints3DLossFn.apply(pred, gt)
 
 
 TERM_BONE, TERM_ANGLE = 1, 2

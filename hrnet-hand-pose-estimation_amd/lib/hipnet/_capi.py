@@ -148,10 +148,13 @@ _SIGS = {
     'hrnet_decode_expectation_bwd': [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp],
     'hrnet_decode_argmax': [_c_vp] * 3 + [_c_int] * 4 + [_c_vp],
     'hrnet_triangulate': [_c_vp] * 6 + [_c_int] * 3 + [_c_vp],
+    'hrnet_triangulate_bwd': [_c_vp] * 7 + [_c_int] * 3 + [_c_vp],
     'hrnet_triangulate_ransac': [_c_vp] * 4 + [_c_int] * 2 + [ctypes.c_double] + [_c_vp] * 3 + [_c_int] * 3 +
                                 [_c_vp],
     'hrnet_joints_loss_fwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
+    'hrnet_joints3d_loss_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],
+    'hrnet_joints3d_loss_bwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_structure_loss': [_c_vp] * 6 + [_c_int] * 4 + [_c_vp],
     'hrnet_structure_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_adam_step': [_c_vp] * 4 + [_c_i64] + [_c_float] * 5 + [_c_int, _c_float, _c_vp],

@@ -11,13 +11,43 @@ random start is not reproduced.
 triangulate_ransac_batch is the reference's RANSAC over the views (lib/utils/misc.py:178-240, direct_optimization off)
 on hrnet_triangulate_ransac, again one launch per batch. The host chooses the hypotheses (view pairs) and the kernel draws
 nothing: by default every pair of views in lexicographic order, which is deterministic and sees every set that the
-reference's ten random draws can see; sample_view_pairs gives the draws the reference would make from a seed."""
+reference's ten random draws can see; sample_view_pairs gives the draws the reference would make from a seed.
+
+triangulate_batch_of_points is differentiable in the points and the confidences (the reference trains through
+torch.svd, AlgebraicTriangulationNet): when one of them requires a gradient the same hrnet_triangulate launch runs
+inside an autograd function whose backward is ONE hrnet_triangulate_bwd launch, which recomputes the SVD from the saved
+inputs. The projection matrices and `to_frame` are constants. triangulate_ransac_batch is not differentiable."""
 import itertools
 import random
 
 import torch
 
 from hipnet import _capi as C
+
+
+class _TriangulateFn(torch.autograd.Function):
+    """X of hrnet_triangulate; backward: hrnet_triangulate_bwd on the saved inputs. pts / conf are f32 contiguous,
+    proj / mat f64 contiguous device tensors; conf and mat may be None."""
+
+    @staticmethod
+    def forward(ctx, pts, conf, proj, mat):
+        B, V, K = pts.shape[:3]
+        X = torch.empty((B, K, 3), dtype=torch.float32, device=pts.device)
+        C.call('hrnet_triangulate', pts.data_ptr(), C.ptr(mat), proj.data_ptr(), C.ptr(conf), X.data_ptr(), None,
+               B, V, K, C.stream_ptr())
+        ctx.save_for_backward(pts, conf, proj, mat)
+        return X
+
+    @staticmethod
+    def backward(ctx, gX):
+        pts, conf, proj, mat = ctx.saved_tensors
+        B, V, K = pts.shape[:3]
+        gX = gX.contiguous().float()
+        dpts = torch.empty_like(pts)
+        dconf = torch.empty_like(conf) if conf is not None and ctx.needs_input_grad[1] else None
+        C.call('hrnet_triangulate_bwd', pts.data_ptr(), C.ptr(mat), proj.data_ptr(), C.ptr(conf), gX.data_ptr(),
+               dpts.data_ptr(), C.ptr(dconf), B, V, K, C.stream_ptr())
+        return dpts, dconf, None, None
 
 
 def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_batch=None, to_frame=None,
@@ -27,7 +57,11 @@ def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_
 
     to_frame (B * V, 2, 3) or None: affine from the points' pixels (heat-map pixels) to the frames of the projection
     matrices, applied first (the readers' `hm_inverse`). return_frame_points=True also returns the mapped 2-D points,
-    (B, V, K, 2) float32. A point with fewer than two views of nonzero confidence is NaN."""
+    (B, V, K, 2) float32 (never part of the graph). A point with fewer than two views of nonzero confidence is NaN.
+
+    Differentiable in points_batch and confidences_batch: when one of them requires a gradient (and gradients are
+    enabled) X carries a grad_fn whose backward is one hrnet_triangulate_bwd launch; X is the same bits either way.
+    A view of zero confidence gets zero gradients, a NaN point NaN gradients in its own views only."""
     if points_batch.ndim != 4 or points_batch.shape[-1] != 2:
         raise ValueError('points_batch: expected (B, V, K, 2), got {}'.format(tuple(points_batch.shape)))
     B, V, K = points_batch.shape[:3]
@@ -42,10 +76,20 @@ def triangulate_batch_of_points(proj_matricies_batch, points_batch, confidences_
     if not all(t.is_cuda for t in tensors):
         raise RuntimeError('triangulate_batch_of_points: expected HIP-device tensors (no CPU path in this build)')
     dev = points_batch.device
-    pts = points_batch.detach().to(dev, torch.float32).contiguous()
     proj = proj_matricies_batch.detach().to(dev, torch.float64).contiguous()
-    conf = None if confidences_batch is None else confidences_batch.detach().to(dev, torch.float32).contiguous()
     mat = None if to_frame is None else to_frame.detach().to(dev, torch.float64).contiguous()
+    if torch.is_grad_enabled() and (points_batch.requires_grad or
+                                    (confidences_batch is not None and confidences_batch.requires_grad)):
+        pts = points_batch.to(dev, torch.float32).contiguous()
+        conf = None if confidences_batch is None else confidences_batch.to(dev, torch.float32).contiguous()
+        X = _TriangulateFn.apply(pts, conf, proj, mat)
+        if not return_frame_points:
+            return X
+        # the mapped points are an extra output of the same kernel: a second, detached launch, off the training path
+        return X, triangulate_batch_of_points(proj, pts.detach(), None if conf is None else conf.detach(), mat,
+                                              True)[1]
+    pts = points_batch.detach().to(dev, torch.float32).contiguous()
+    conf = None if confidences_batch is None else confidences_batch.detach().to(dev, torch.float32).contiguous()
     X = torch.empty((B, K, 3), dtype=torch.float32, device=dev)
     frame = torch.empty((B, V, K, 2), dtype=torch.float32, device=dev) if return_frame_points else None
     C.call('hrnet_triangulate', pts.data_ptr(), C.ptr(mat), proj.data_ptr(), C.ptr(conf), X.data_ptr(), C.ptr(frame),

@@ -579,6 +579,26 @@ int hrnet_triangulate(const float* pts, const double* to_frame, const double* pr
                       float* pts_frame, int B, int V, int K, hr_stream_t stream);
 
 /*
+ * Backward of hrnet_triangulate for the 3-D training loss (the reference back-propagates through torch.svd,
+ * lib/models/triangulation_model_utils/multiview.py:142-169). pts, to_frame, proj, conf and B, V, K are the forward's
+ * inputs, unchanged; nothing else is saved: the f64 Givens QR + Jacobi SVD is recomputed with the forward's device
+ * code, which yields all four right singular vectors v_j and squared singular values n_j (A^T A is never formed).
+ *   gX    [B,K,3] f32: dL/dX
+ *   dpts  [B,V,K,2] f32: dL/d pts, the GIVEN points (through the 2 x 2 part of to_frame when there is one)
+ *   dconf [B,V,K] f32 or NULL: dL/d conf (for conf NULL: with respect to a unit weight)
+ * With h = v_m the forward's vector, g^ = [g / h3, -(g . h[0:3]) / h3^2] and z = -sum_{j != m} v_j (v_j . g^) /
+ * (n_j - n_m): dL/dA = (A z) h^T + (A h) z^T, and for view v with weight c and rows a0 = x P[2] - P[0], a1 = y P[2] -
+ * P[1]: dL/dx = c^2 ((a0 . z)(h . P[2]) + (a0 . h)(z . P[2])), dL/dy the same with a1, dL/dc = 2 c ((a0 . z)(a0 . h) +
+ * (a1 . z)(a1 . h)). One launch for any B, one thread per point, f32 in and out, f64 inside, 2 <= V <= 8.
+ * A view of weight 0 gets dpts = 0 and dconf = 0 exactly. A point whose X is NaN in the forward (fewer than two views
+ * of nonzero weight, or a non-finite input) gets NaN in every view of that point and nowhere else. A vanishing gap
+ * n_j - n_m gives the huge or non-finite values of the formula, as the reference's SVD backward does: they are
+ * returned, not clamped. Nothing traps.
+ */
+int hrnet_triangulate_bwd(const float* pts, const double* to_frame, const double* proj, const float* conf,
+                          const float* gX, float* dpts, float* dconf, int B, int V, int K, hr_stream_t stream);
+
+/*
  * RANSAC over the views, then the DLT of hrnet_triangulate over the chosen views (reference lib/utils/misc.py:178-240
  * with direct_optimization off, as RANSACTriangulationNet.forward calls it). pts, to_frame, proj, pts_frame and
  * B, V, K as in hrnet_triangulate; there are no weights.
@@ -620,6 +640,16 @@ int hrnet_joints_loss_fwd(const float* pred, const float* gt, const float* vis, 
                           int K, hr_stream_t stream);
 int hrnet_joints_loss_bwd(const float* pred, const float* gt, const float* vis, const float* gout,
                           float* dpred, int B, int K, hr_stream_t stream);
+
+/*
+ * Joints3DMSELoss (lib/core/loss.py:137-148) of the 3-D training step: sum over batch and joints of
+ * ||gt - pred||_2, over K - a sum over the batch, as the reference computes it. pred/gt [B,K,3] f32, loss[0] f32; f64
+ * inside, summed in a fixed order (a call is bit-reproducible). backward: dpred = *gout / K * (pred - gt) /
+ * ||pred - gt||, 0 for a zero difference (torch.norm backward); gout is a device scalar.
+ */
+int hrnet_joints3d_loss_fwd(const float* pred, const float* gt, float* loss, int B, int K, hr_stream_t stream);
+int hrnet_joints3d_loss_bwd(const float* pred, const float* gt, const float* gout, float* dpred, int B, int K,
+                            hr_stream_t stream);
 
 /*
  * Hand-structure regularisers of the 2-D training step: BoneLengthLoss and JointAngleLoss (lib/core/loss.py:150-223)
