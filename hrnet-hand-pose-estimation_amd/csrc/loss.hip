@@ -28,24 +28,41 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return m;
 }
 
-// spatial softmax with temperature, one block per (batch, joint) map (pose_hrnet_softmax.py:520-524)
+// the same fixed order as block_sum (lanes by xor butterfly, then the waves in order), in f64
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) s += red[k];
+  __syncthreads();
+  return s;
+}
+
+// spatial softmax with temperature, one block per (batch, joint) map (pose_hrnet_softmax.py:520-524). The normaliser is
+// summed and applied in f64, so that an output carries the rounding of its exp and one more. (A nearly one-hot map has
+// the normaliser just above 1: every f32 addition of the block sum then rounds by 2^-24 of the largest output, and the
+// output near 1 came out more than 4 * 2^-24 off.)
 __global__ __launch_bounds__(256) void spatial_softmax_fwd_kernel(const float* x, const float* temp, float* out,
                                                                   int HW) {
   __shared__ float red[4];
+  __shared__ double red64[4];
   const size_t base = (size_t)blockIdx.x * HW;
   const float t = temp[0];
   float m = -INFINITY;
   for (int i = threadIdx.x; i < HW; i += 256) m = fmaxf(m, x[base + i] * t);
   m = block_max(m, red);
-  float s = 0.f;
+  double s = 0.0;
   for (int i = threadIdx.x; i < HW; i += 256) {
     const float e = expf(x[base + i] * t - m);
     out[base + i] = e;
-    s += e;
+    s += (double)e;
   }
-  s = block_sum(s, red);
-  const float inv = 1.f / s;
-  for (int i = threadIdx.x; i < HW; i += 256) out[base + i] *= inv;
+  s = block_sum_f64(s, red64);
+  const double inv = 1.0 / s;
+  for (int i = threadIdx.x; i < HW; i += 256) out[base + i] = (float)((double)out[base + i] * inv);
 }
 
 __global__ __launch_bounds__(256) void spatial_softmax_bwd_kernel(const float* x, const float* out,
@@ -533,7 +550,8 @@ extern "C" int hrnet_heatmap_loss_fwd(const float* pred, const float* gt, float*
 
 extern "C" int hrnet_heatmap_loss_bwd(const float* pred, const float* gt, const float* gout,
                                       float* dpred, int BK, int HW, int mode, hr_stream_t stream) {
-  HR_REQUIRE(pred && gt && gout && dpred && BK > 0 && HW > 0, "heatmap_loss_bwd: args");
+  HR_REQUIRE(pred && gt && gout && dpred && BK > 0 && HW > 0 && (mode == 0 || mode == 1),
+             "heatmap_loss_bwd: args");
   const long long n = (long long)BK * HW;
   long long grid = (n + 255) / 256;
   if (grid > 4096) grid = 4096;
@@ -586,7 +604,7 @@ extern "C" int hrnet_decode_expectation(const float* hms, float* preds, int BK, 
 
 extern "C" int hrnet_decode_expectation_bwd(const float* gpreds, float* dhms, int BK, int H, int W,
                                             int accumulate, hr_stream_t stream) {
-  HR_REQUIRE(gpreds && dhms && BK > 0, "decode_expectation_bwd: args");
+  HR_REQUIRE(gpreds && dhms && BK > 0 && H > 0 && W > 0, "decode_expectation_bwd: args");
   hipLaunchKernelGGL(decode_expect_bwd_kernel, dim3(BK), dim3(256), 0, (hipStream_t)stream, gpreds, dhms,
                      H, W, accumulate);
   return hr_check_launch("decode_expectation_bwd");

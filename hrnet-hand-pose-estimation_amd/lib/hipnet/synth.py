@@ -78,7 +78,8 @@ IMAGENET_STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
 
 
 def gaussian_heatmaps(pose2d, visibility, hm_h=64, hm_w=64, sigma=2):
-    """Un-normalised Gaussians, peak 1 at int(coord), window 6*sigma+3."""
+    """Un-normalised Gaussians, peak 1 at int(coord), window 6*sigma+3. A joint is drawn where its visibility is
+    > 0 (the reference's `pt[2] > 0`); visibility None draws every joint."""
     b, k = pose2d.shape[:2]
     size = 6 * sigma + 3
     g1 = np.arange(size, dtype=np.float32)
@@ -87,7 +88,7 @@ def gaussian_heatmaps(pose2d, visibility, hm_h=64, hm_w=64, sigma=2):
     hms = np.zeros((b, k, hm_h, hm_w), dtype=np.float32)
     for i in range(b):
         for j in range(k):
-            if not visibility[i, j, 0]:
+            if visibility is not None and not visibility[i, j, 0] > 0:
                 continue
             x, y = int(pose2d[i, j, 0]), int(pose2d[i, j, 1])
             if x < 0 or y < 0 or x >= hm_w or y >= hm_h:
