@@ -9,13 +9,16 @@ BoneLengthLoss sum over batch and j = 1..20 of (|gt[j]-gt[j-1]| - |pred[j]-pred[
                finger-base branch is never taken)
 JointAngleLoss sum over batch and fingers (joints 4f..4f+4) of d^2 for each negative product d of neighbouring
                bone cross products (z components; the coplanarity rule is identically zero for 2-D poses)
+VolumetricCELoss  the volumetric models' regulariser (reference :225-256): -log of the predicted volume at the voxel
+               nearest the ground truth, validity-weighted, over the number of joints; the nearest-voxel search
+               and the sum are one call (hrnet_volumetric_ce_loss), f64 inside, fixed summation order
 structure_losses  what the training loop calls: both terms after scale_pose2d (relative to the wrist, divided by
                the wrist-to-joint-9 length, no epsilon) of pred and gt, ONE launch (hrnet_structure_loss) that also
                leaves d bone / d pred and d angle / d pred when pred requires grad; backward is one launch that
                combines them with the upstream gradients, nothing is recomputed
 
 All are autograd Functions over the C ABI (hrnet_heatmap_loss_*, hrnet_joints_loss_*, hrnet_joints3d_loss_*,
-hrnet_structure_loss*);
+hrnet_structure_loss*, hrnet_volumetric_ce_loss*);
 inputs must be HIP tensors - there is no CPU path. The structure terms take B x 21 x 2 poses only: 3-D poses (a real
 z, the reference's other use of the two classes) are refused.
 
@@ -137,6 +140,56 @@ class Joints3DMSELoss(nn.Module):
             raise ValueError('Joints3DMSELoss expects two B x K x 3 poses, got {} and {}'.format(
                 tuple(pred.shape), tuple(gt.shape)))
         return _Joints3DLossFn.apply(pred, gt)
+
+
+class _VolumetricCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, coord, gt, validity):
+        B, J, X, Y, Z = p.shape
+        loss = torch.empty(1, dtype=torch.float32, device=p.device)
+        idx = torch.empty((B, J), dtype=torch.int32, device=p.device)
+        C.call('hrnet_volumetric_ce_loss', coord.data_ptr(), p.data_ptr(), gt.data_ptr(), validity.data_ptr(),
+               loss.data_ptr(), idx.data_ptr(), B, J, X, Y, Z, C.stream_ptr())
+        ctx.save_for_backward(p, validity, idx)
+        ctx.mark_non_differentiable(idx)
+        return loss.reshape(()), idx
+
+    @staticmethod
+    def backward(ctx, gout, _gidx):
+        p, validity, idx = ctx.saved_tensors
+        B, J, X, Y, Z = p.shape
+        dp = torch.empty_like(p)
+        g = gout.contiguous().float().reshape(1)
+        C.call('hrnet_volumetric_ce_loss_bwd', p.data_ptr(), validity.data_ptr(), idx.data_ptr(), g.data_ptr(),
+               dp.data_ptr(), B, J, X, Y, Z, C.stream_ptr())
+        return dp, None, None, None
+
+
+class VolumetricCELoss(nn.Module):
+    """The volumetric cross-entropy regulariser (reference :225-256): per joint the voxel of the coordinate volume
+    nearest the ground truth (f64 distances, the first of equals), then sum validity * -log(p[voxel] + 1e-6) over the
+    number of joints, valid or not. coord_volumes_batch B x X x Y x Z x 3, volumes_batch_pred B x J x X x Y x Z (the
+    second output of integrate_tensor_3d_with_coordinates), keypoints_gt B x J x 3, keypoints_binary_validity
+    B x J x 1 as the reference indexes it (B x J is taken too). forward returns the loss, as the reference;
+    loss_and_indices also returns the chosen flat voxel indices x*Y*Z + y*Z + z (B x J int32). No state is kept."""
+
+    def forward(self, coord_volumes_batch, volumes_batch_pred, keypoints_gt, keypoints_binary_validity):
+        return self.loss_and_indices(coord_volumes_batch, volumes_batch_pred, keypoints_gt,
+                                     keypoints_binary_validity)[0]
+
+    def loss_and_indices(self, coord_volumes_batch, volumes_batch_pred, keypoints_gt, keypoints_binary_validity):
+        p = _dev_f32(volumes_batch_pred, 'VolumetricCELoss')
+        if p.dim() != 5:
+            raise ValueError('VolumetricCELoss expects B x J x X x Y x Z volumes, got {}'.format(tuple(p.shape)))
+        B, J = p.shape[:2]
+        coord = _dev_f32(coord_volumes_batch, 'VolumetricCELoss').detach()
+        gt = _dev_f32(keypoints_gt, 'VolumetricCELoss').detach()
+        validity = _dev_f32(keypoints_binary_validity, 'VolumetricCELoss').detach()
+        if tuple(coord.shape) != (B,) + tuple(p.shape[2:]) + (3,) or tuple(gt.shape) != (B, J, 3) \
+                or validity.numel() != B * J:
+            raise ValueError('VolumetricCELoss: coord volumes {}, volumes {}, key points {}, validity {}'.format(
+                tuple(coord.shape), tuple(p.shape), tuple(gt.shape), tuple(validity.shape)))
+        return _VolumetricCEFn.apply(p, coord, gt, validity.reshape(B, J))
 
 
 TERM_BONE, TERM_ANGLE = 1, 2

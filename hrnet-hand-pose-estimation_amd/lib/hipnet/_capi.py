@@ -151,6 +151,12 @@ _SIGS = {
     'hrnet_triangulate_bwd': [_c_vp] * 7 + [_c_int] * 3 + [_c_vp],
     'hrnet_triangulate_ransac': [_c_vp] * 4 + [_c_int] * 2 + [ctypes.c_double] + [_c_vp] * 3 + [_c_int] * 3 +
                                 [_c_vp],
+    'hrnet_unproject_volume': [_c_vp] * 5 + [_c_int] * 9 + [_c_vp],
+    'hrnet_unproject_volume_bwd': [_c_vp] * 7 + [_c_int] * 9 + [_c_vp],
+    'hrnet_volume_integrate': [_c_vp] * 2 + [_c_float, _c_int] + [_c_vp] * 3 + [_c_int] * 5 + [_c_vp],
+    'hrnet_volume_integrate_bwd': [_c_vp] * 5 + [_c_float, _c_int] + [_c_vp] * 2 + [_c_int] * 5 + [_c_vp],
+    'hrnet_volumetric_ce_loss': [_c_vp] * 6 + [_c_int] * 5 + [_c_vp],
+    'hrnet_volumetric_ce_loss_bwd': [_c_vp] * 5 + [_c_int] * 5 + [_c_vp],
     'hrnet_joints_loss_fwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints3d_loss_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],

@@ -622,6 +622,82 @@ int hrnet_triangulate_ransac(const float* pts, const double* to_frame, const dou
                              int V, int K, hr_stream_t stream);
 
 /*
+ * Volumetric lifting (csrc/volumetric.hip). All tensors f32 in the reference's module contract: features [B,V,C,H,W],
+ * volumes [B,C,X,Y,Z], coordinate volumes [B,X,Y,Z,3] (world coordinates of the voxel centres), projections [B,V,3,4].
+ * Element offsets are 64-bit. Limits of all six entries: 1 <= V <= 8, B <= 65535, X*Y*Z <= 2^30, H*W <=
+ * HR_VOLUME_MAX_MAP (a 64-bit fixed-point plane of the backward must fit the LDS), B*J <= 65535; anything else is
+ * HR_E_BADARG.
+ */
+#define HR_VOL_SUM 0
+#define HR_VOL_MAX 1
+#define HR_VOL_SOFTMAX 2
+#define HR_VOL_CONF 3
+#define HR_VOLUME_MAX_MAP 16384 /* H*W of a feature map: 128 KB of LDS as 64-bit cells (96x72 is 6912) */
+#define HR_VOLUME_SPLIT 32      /* workgroups per map of hrnet_volume_integrate*: `work` holds B*J*32*5 doubles */
+
+/*
+ * unproject_heatmaps (reference lib/models/triangulation_model_utils/op.py:99-168), one launch for any B and V.
+ * Per voxel p and view v: q = P[b,v] [p,1]; the view is invalid where q.z <= 0 (a q.z of exactly 0 becomes 1 before
+ * the divide, op.py:124); u = q.x/q.z, w = q.y/q.z. The sample position is the REFERENCE'S rule, not a pixel-exact
+ * one: op.py:129-130 normalises gx = 2(u/H - 0.5), gy = 2(w/W - 0.5) with (H, W) = heatmap_shape - the divisors are
+ * swapped - and F.grid_sample(align_corners=True) then reads column u (W-1)/H and row w (H-1)/W. Bilinear, zero
+ * padding (a corner outside the map contributes 0); the sample is 0 where the view is invalid. The projection and the
+ * split into cell and fractional weights are f64 from the f32 inputs, the blend and the aggregation f32.
+ *   method HR_VOL_SUM: sum_v s_v; HR_VOL_MAX: the largest sample; HR_VOL_SOFTMAX: sum_v s_v softmax_v(s)_v over the V
+ *   samples, zeros of invalid or out-of-image views included (op.py:158-164); HR_VOL_CONF: sum_v conf[b,v,c] s_v
+ *   (op.py:152-153), conf [B,V,C] f32 (NULL otherwise), not normalised here.
+ */
+int hrnet_unproject_volume(const float* features, const float* proj, const float* coord, const float* conf,
+                           float* volumes, int method, int B, int V, int C, int H, int W, int X, int Y, int Z,
+                           hr_stream_t stream);
+
+/*
+ * Backward of hrnet_unproject_volume (the reference's autograd through op.py:99-168) from gV [B,C,X,Y,Z]: dfeatures
+ * [B,V,C,H,W], overwritten, and dconf [B,V,C] for HR_VOL_CONF (NULL otherwise, or when not wanted). Positions and
+ * samples are recomputed from the forward's inputs. A view's sample gets gV times: sum 1; max 1 for the first largest
+ * view, 0 for the others; softmax x_v (1 + s_v - sum_u s_u x_u), x = softmax_v(s); conf the weight. The projection
+ * matrices and the coordinate volume are constants (no gradient - a deviation: the reference's grid_sample would
+ * reach the cuboid through its grid gradient). One launch; a workgroup owns (b, v, 1..4 channels), accumulates the
+ * scatter in LDS planes in 64-bit fixed point with integer atomics and stores them with plain stores: the result is
+ * the same bits on every run. A non-finite gV[b,c], conf or feature plane gives a NaN dfeatures plane.
+ */
+int hrnet_unproject_volume_bwd(const float* features, const float* proj, const float* coord, const float* conf,
+                               const float* gV, float* dfeatures, float* dconf, int method, int B, int V, int C, int H,
+                               int W, int X, int Y, int Z, hr_stream_t stream);
+
+/*
+ * integrate_tensor_3d_with_coordinates (reference lib/models/triangulation_model_utils/op.py:84-96) with the model's
+ * `volumes * VOLUME_MULTIPLIER` folded in: vols [B,J,X,Y,Z], coord [B,X,Y,Z,3].
+ *   softmax != 0: p = softmax(multiplier * vols) over the X*Y*Z voxels of each map (the map's maximum is subtracted);
+ *   softmax == 0: p = relu(multiplier * vols), not normalised.
+ * keypoints [B,J,3] = sum p coord; p [B,J,X,Y,Z]. f32 in and out; the maximum, the sum and the three moments are f64,
+ * computed as HR_VOLUME_SPLIT partials per map and merged in index order (a call is bit-reproducible).
+ * work: B*J*HR_VOLUME_SPLIT*5 doubles of device scratch, contents undefined afterwards. Two launches.
+ * backward, from gK [B,J,3] and gP [B,J,X,Y,Z] or NULL (zero), with t_i = gK . coord_i + gP_i:
+ *   softmax: dvols_i = multiplier p_i (t_i - sum_j p_j t_j); relu: dvols_i = multiplier [multiplier vols_i > 0] t_i.
+ * p is the forward's output; coord is a constant.
+ */
+int hrnet_volume_integrate(const float* vols, const float* coord, float multiplier, int softmax, float* keypoints,
+                           float* p, double* work, int B, int J, int X, int Y, int Z, hr_stream_t stream);
+int hrnet_volume_integrate_bwd(const float* vols, const float* p, const float* coord, const float* gK, const float* gP,
+                               float multiplier, int softmax, float* dvols, double* work, int B, int J, int X, int Y,
+                               int Z, hr_stream_t stream);
+
+/*
+ * VolumetricCELoss (reference lib/core/loss.py:225-256): per (b,j) the voxel of coord[b] nearest gt[b,j] (f64
+ * distances, the first of equal distances wins) -> idx [B,J] int32, the flat index x*Y*Z + y*Z + z;
+ * loss[0] = sum_{b,j} validity[b,j] (-log(p[b,j,idx] + 1e-6)) / (B*J) - the divisor counts every joint, valid or not,
+ * as the reference does - f64 inside, summed in a fixed order. coord [B,X,Y,Z,3], p [B,J,X,Y,Z], gt [B,J,3],
+ * validity [B,J].
+ * backward: dp [B,J,X,Y,Z] is zeroed (hrnet_fill_zero) and dp[b,j,idx] = -*gout validity / (p + 1e-6) / (B*J);
+ * gout is a device scalar, idx the forward's.
+ */
+int hrnet_volumetric_ce_loss(const float* coord, const float* p, const float* gt, const float* validity, float* loss,
+                             int* idx, int B, int J, int X, int Y, int Z, hr_stream_t stream);
+int hrnet_volumetric_ce_loss_bwd(const float* p, const float* validity, const int* idx, const float* gout, float* dp,
+                                 int B, int J, int X, int Y, int Z, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
