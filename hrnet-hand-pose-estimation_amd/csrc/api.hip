@@ -29,7 +29,7 @@ int hr_check_launch(const char* what) {
 }
 
 extern "C" const char* hrnet_last_error_string(void) { return g_err; }
-// 2: HR_OP_CONV i[17] (route), HR_OP_WGRAD i[12..15], HrPackEnt.ld, the head / table op kinds of round 3
+// 2: HR_CONV_I_ROUTE, HR_WGRAD_I_ATOMIC .. HR_WGRAD_I_LD, HrPackEnt.ld, the head / table op kinds of round 3
 extern "C" int hrnet_abi_version(void) { return 2; }
 
 static int run_one(const HrOp& op, hipStream_t s, int k) {
@@ -63,11 +63,11 @@ static int run_one(const HrOp& op, hipStream_t s, int k) {
     case HR_OP_HEAD_BWD: e = hr_launch_head_bwd(op, s); break;
     case HR_OP_POOL_REDUCE: e = hr_launch_pool_reduce(op, s); break;
     case HR_OP_EVENT_RECORD:
-      e = hipEventRecord((hipEvent_t)op.p[0], s) == hipSuccess ? HR_OK : HR_E_LAUNCH;
+      e = hipEventRecord((hipEvent_t)op.p[HR_EVENT_P_EVENT], s) == hipSuccess ? HR_OK : HR_E_LAUNCH;
       if (e) hr_set_error("event record failed");
       break;
     case HR_OP_STREAM_WAIT:
-      e = hipStreamWaitEvent(s, (hipEvent_t)op.p[0], 0) == hipSuccess ? HR_OK : HR_E_LAUNCH;
+      e = hipStreamWaitEvent(s, (hipEvent_t)op.p[HR_EVENT_P_EVENT], 0) == hipSuccess ? HR_OK : HR_E_LAUNCH;
       if (e) hr_set_error("stream wait failed");
       break;
     default:
@@ -156,33 +156,35 @@ extern "C" int hrnet_wgrad_reduce(const float* slabs, float* grad_oihw, int nspl
                                   int ks, int Cout_real, int Cin_real, int kflat, int accumulate,
                                   hr_stream_t stream) {
   OP_BEGIN(HR_OP_WGRAD_REDUCE);
-  const int iv[8] = {nsplit, Cout, Cin, ks, Cout_real, Cin_real, kflat, accumulate};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)slabs; op.p[1] = grad_oihw;
+  op.i[HR_WGRAD_REDUCE_I_NSPLIT] = nsplit; op.i[HR_WGRAD_REDUCE_I_COUT_PAD] = Cout;
+  op.i[HR_WGRAD_REDUCE_I_CIN_PAD] = Cin; op.i[HR_WGRAD_REDUCE_I_KS] = ks; op.i[HR_WGRAD_REDUCE_I_COUT] = Cout_real;
+  op.i[HR_WGRAD_REDUCE_I_CIN] = Cin_real; op.i[HR_WGRAD_REDUCE_I_KFLAT] = kflat;
+  op.i[HR_WGRAD_REDUCE_I_ACCUMULATE] = accumulate;
+  op.p[HR_WGRAD_REDUCE_P_SLABS] = (void*)slabs; op.p[HR_WGRAD_REDUCE_P_GRAD] = grad_oihw;
   return hr_launch_wgrad_reduce(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_pack_weights(int dtype, const float* w_oihw, void* packed, int Cout, int Cin, int ks,
                                   int Cout_pad, int Cin_pad, int mode, hr_stream_t stream) {
   OP_BEGIN(HR_OP_PACK_WEIGHTS);
-  const int iv[7] = {dtype, Cout, Cin, ks, Cout_pad, Cin_pad, mode};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)w_oihw; op.p[1] = packed;
+  op.i[HR_PACK_I_DTYPE] = dtype; op.i[HR_PACK_I_COUT] = Cout; op.i[HR_PACK_I_CIN] = Cin; op.i[HR_PACK_I_KS] = ks;
+  op.i[HR_PACK_I_COUT_PAD] = Cout_pad; op.i[HR_PACK_I_CIN_PAD] = Cin_pad; op.i[HR_PACK_I_MODE] = mode;
+  op.p[HR_PACK_P_SRC] = (void*)w_oihw; op.p[HR_PACK_P_PACKED] = packed;
   return hr_launch_pack_weights(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_pack_weights_table(int dtype, const HrPackEnt* table, int n, int total_blocks,
                                         hr_stream_t stream) {
   OP_BEGIN(HR_OP_PACK_TABLE);
-  op.i[0] = dtype; op.i[1] = n; op.i[2] = total_blocks;
-  op.p[0] = (void*)table;
+  op.i[HR_PACK_TABLE_I_DTYPE] = dtype; op.i[HR_PACK_TABLE_I_N] = n; op.i[HR_PACK_TABLE_I_BLOCKS] = total_blocks;
+  op.p[HR_PACK_TABLE_P_TABLE] = (void*)table;
   return hr_launch_pack_table(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_wgrad_reduce_table(const HrWredEnt* table, int n, int total_blocks, hr_stream_t stream) {
   OP_BEGIN(HR_OP_WGRAD_REDUCE_TABLE);
-  op.i[0] = n; op.i[1] = total_blocks;
-  op.p[0] = (void*)table;
+  op.i[HR_TABLE_I_N] = n; op.i[HR_TABLE_I_BLOCKS] = total_blocks;
+  op.p[HR_TABLE_P_TABLE] = (void*)table;
   return hr_launch_wgrad_reduce_table(op, (hipStream_t)stream);
 }
 
@@ -192,11 +194,13 @@ extern "C" int hrnet_bn_finalize(const float* stats, int tiles, int C, float cou
                                  float* scale, float* shift, float* save_mean, float* save_invstd,
                                  hr_stream_t stream) {
   OP_BEGIN(HR_OP_BN_FINALIZE);
-  op.i[0] = tiles; op.i[1] = C; op.i[2] = training;
-  op.f[0] = count; op.f[1] = momentum; op.f[2] = eps;
-  op.p[0] = (void*)stats; op.p[1] = (void*)gamma; op.p[2] = (void*)beta; op.p[3] = running_mean;
-  op.p[4] = running_var; op.p[5] = num_batches_tracked; op.p[6] = scale; op.p[7] = shift;
-  op.p[8] = save_mean; op.p[9] = save_invstd;
+  op.i[HR_BN_FINALIZE_I_TILES] = tiles; op.i[HR_BN_FINALIZE_I_C] = C; op.i[HR_BN_FINALIZE_I_TRAINING] = training;
+  op.f[HR_BN_FINALIZE_F_COUNT] = count; op.f[HR_BN_FINALIZE_F_MOMENTUM] = momentum; op.f[HR_BN_FINALIZE_F_EPS] = eps;
+  op.p[HR_BN_FINALIZE_P_STATS] = (void*)stats; op.p[HR_BN_FINALIZE_P_GAMMA] = (void*)gamma;
+  op.p[HR_BN_FINALIZE_P_BETA] = (void*)beta; op.p[HR_BN_FINALIZE_P_RUNNING_MEAN] = running_mean;
+  op.p[HR_BN_FINALIZE_P_RUNNING_VAR] = running_var; op.p[HR_BN_FINALIZE_P_NUM_BATCHES_TRACKED] = num_batches_tracked;
+  op.p[HR_BN_FINALIZE_P_SCALE] = scale; op.p[HR_BN_FINALIZE_P_SHIFT] = shift;
+  op.p[HR_BN_FINALIZE_P_SAVE_MEAN] = save_mean; op.p[HR_BN_FINALIZE_P_SAVE_INVSTD] = save_invstd;
   return hr_launch_bn_finalize(op, (hipStream_t)stream);
 }
 
@@ -206,15 +210,15 @@ extern "C" int hrnet_sum_terms(int dtype, void* out, int N, int Ho, int Wo, int 
                                int relu_out, hr_stream_t stream) {
   OP_BEGIN(HR_OP_SUM_TERMS);
   HR_REQUIRE(nterms >= 1 && nterms <= 4 && src && shifts && relus, "sum_terms: args");
-  const int iv[7] = {dtype, N, Ho, Wo, C, nterms, relu_out};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = out;
+  op.i[HR_SUM_I_DTYPE] = dtype; op.i[HR_SUM_I_N] = N; op.i[HR_SUM_I_H] = Ho; op.i[HR_SUM_I_W] = Wo;
+  op.i[HR_SUM_I_C] = C; op.i[HR_SUM_I_NTERMS] = nterms; op.i[HR_SUM_I_RELU_OUT] = relu_out;
+  op.p[HR_SUM_P_OUT] = out;
   for (int t = 0; t < nterms; ++t) {
-    op.i[7 + t] = shifts[t];
-    op.i[11 + t] = relus[t];
-    op.p[1 + t] = (void*)src[t];
-    op.p[5 + t] = scale ? (void*)scale[t] : nullptr;
-    op.p[9 + t] = shift ? (void*)shift[t] : nullptr;
+    op.i[HR_SUM_I_SH0 + t] = shifts[t];
+    op.i[HR_SUM_I_RELU0 + t] = relus[t];
+    op.p[HR_SUM_P_SRC0 + t] = (void*)src[t];
+    op.p[HR_SUM_P_SCALE0 + t] = scale ? (void*)scale[t] : nullptr;
+    op.p[HR_SUM_P_SHIFT0 + t] = shift ? (void*)shift[t] : nullptr;
   }
   return hr_launch_sum_terms(op, (hipStream_t)stream);
 }
@@ -225,26 +229,26 @@ extern "C" int hrnet_sum_terms_bnref(int dtype, void* out, int N, int Ho, int Wo
                                      const float* inv_counts, float eps, hr_stream_t stream) {
   OP_BEGIN(HR_OP_SUM_TERMS);
   HR_REQUIRE(nterms >= 1 && nterms <= 4 && src && shifts && relus && scale && shift && inv_counts, "sum_terms: args");
-  const int iv[7] = {dtype, N, Ho, Wo, C, nterms, relu_out};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = out;
+  op.i[HR_SUM_I_DTYPE] = dtype; op.i[HR_SUM_I_N] = N; op.i[HR_SUM_I_H] = Ho; op.i[HR_SUM_I_W] = Wo;
+  op.i[HR_SUM_I_C] = C; op.i[HR_SUM_I_NTERMS] = nterms; op.i[HR_SUM_I_RELU_OUT] = relu_out;
+  op.p[HR_SUM_P_OUT] = out;
   for (int t = 0; t < nterms; ++t) {
-    op.i[7 + t] = shifts[t];
-    op.i[11 + t] = relus[t];
-    op.p[1 + t] = (void*)src[t];
-    op.p[5 + t] = (void*)scale[t];
-    op.p[9 + t] = (void*)shift[t];
+    op.i[HR_SUM_I_SH0 + t] = shifts[t];
+    op.i[HR_SUM_I_RELU0 + t] = relus[t];
+    op.p[HR_SUM_P_SRC0 + t] = (void*)src[t];
+    op.p[HR_SUM_P_SCALE0 + t] = (void*)scale[t];
+    op.p[HR_SUM_P_SHIFT0 + t] = (void*)shift[t];
     op.f[t] = inv_counts[t];
   }
-  op.i[15] = sums_mode;
-  memcpy(&op.i[16], &eps, sizeof(float));
+  op.i[HR_SUM_I_SUMS_MODE] = sums_mode;
+  memcpy(&op.i[HR_SUM_I_EPS_BITS], &eps, sizeof(float));
   return hr_launch_sum_terms(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_bn_finalize_table(const HrBnEnt* table, int n, int total_blocks, hr_stream_t stream) {
   OP_BEGIN(HR_OP_BN_FINALIZE_TABLE);
-  op.i[0] = n; op.i[1] = total_blocks;
-  op.p[0] = (void*)table;
+  op.i[HR_TABLE_I_N] = n; op.i[HR_TABLE_I_BLOCKS] = total_blocks;
+  op.p[HR_TABLE_P_TABLE] = (void*)table;
   return hr_launch_bn_finalize_table(op, (hipStream_t)stream);
 }
 
@@ -252,10 +256,13 @@ extern "C" int hrnet_grad_term(int dtype, void* dst, const void* g, const void* 
                                const float* scale, const float* shift, const float* coef, int N, int H,
                                int W, int C, int sh, int inner_relu, int accumulate, hr_stream_t stream) {
   OP_BEGIN(HR_OP_GRAD_TERM);
-  const int iv[8] = {dtype, N, H, W, C, sh, inner_relu, accumulate};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = dst; op.p[1] = (void*)g; op.p[2] = (void*)mask_out; op.p[3] = (void*)y;
-  op.p[4] = (void*)scale; op.p[5] = (void*)shift; op.p[6] = (void*)coef;
+  op.i[HR_GRAD_TERM_I_DTYPE] = dtype; op.i[HR_GRAD_TERM_I_N] = N; op.i[HR_GRAD_TERM_I_H] = H;
+  op.i[HR_GRAD_TERM_I_W] = W; op.i[HR_GRAD_TERM_I_C] = C; op.i[HR_GRAD_TERM_I_SH] = sh;
+  op.i[HR_GRAD_TERM_I_INNER_RELU] = inner_relu; op.i[HR_GRAD_TERM_I_ACCUMULATE] = accumulate;
+  op.p[HR_GRAD_TERM_P_DST] = dst; op.p[HR_GRAD_TERM_P_G] = (void*)g; op.p[HR_GRAD_TERM_P_MASK] = (void*)mask_out;
+  op.p[HR_GRAD_TERM_P_Y] = (void*)y;
+  op.p[HR_GRAD_TERM_P_SCALE] = (void*)scale; op.p[HR_GRAD_TERM_P_SHIFT] = (void*)shift;
+  op.p[HR_GRAD_TERM_P_COEF] = (void*)coef;
   return hr_launch_grad_term(op, (hipStream_t)stream);
 }
 
@@ -263,10 +270,13 @@ extern "C" int hrnet_grad_term2(int dtype, void* dst, void* dst2, const void* g,
                                 const void* y, const float* scale, const float* shift, const float* coef, int N,
                                 int H, int W, int C, int accumulate, int accumulate2, hr_stream_t stream) {
   OP_BEGIN(HR_OP_GRAD_TERM);
-  const int iv[9] = {dtype, N, H, W, C, 0, 0, accumulate, accumulate2};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = dst; op.p[1] = (void*)g; op.p[2] = (void*)mask_out; op.p[3] = (void*)y;
-  op.p[4] = (void*)scale; op.p[5] = (void*)shift; op.p[6] = (void*)coef; op.p[7] = dst2;
+  op.i[HR_GRAD_TERM_I_DTYPE] = dtype; op.i[HR_GRAD_TERM_I_N] = N; op.i[HR_GRAD_TERM_I_H] = H;
+  op.i[HR_GRAD_TERM_I_W] = W; op.i[HR_GRAD_TERM_I_C] = C; op.i[HR_GRAD_TERM_I_ACCUMULATE] = accumulate;
+  op.i[HR_GRAD_TERM_I_ACCUMULATE2] = accumulate2;
+  op.p[HR_GRAD_TERM_P_DST] = dst; op.p[HR_GRAD_TERM_P_G] = (void*)g; op.p[HR_GRAD_TERM_P_MASK] = (void*)mask_out;
+  op.p[HR_GRAD_TERM_P_Y] = (void*)y;
+  op.p[HR_GRAD_TERM_P_SCALE] = (void*)scale; op.p[HR_GRAD_TERM_P_SHIFT] = (void*)shift;
+  op.p[HR_GRAD_TERM_P_COEF] = (void*)coef; op.p[HR_GRAD_TERM_P_DST2] = dst2;
   return hr_launch_grad_term(op, (hipStream_t)stream);
 }
 
@@ -274,10 +284,12 @@ extern "C" int hrnet_bn_bwd_reduce(int dtype, float* partials, const void* g, co
                                    const void* y, const float* scale, const float* shift, int N, int H,
                                    int W, int C, int sh, int inner_relu, hr_stream_t stream) {
   OP_BEGIN(HR_OP_BN_BWD_REDUCE);
-  const int iv[7] = {dtype, N, H, W, C, sh, inner_relu};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = partials; op.p[1] = (void*)g; op.p[2] = (void*)mask_out; op.p[3] = (void*)y;
-  op.p[4] = (void*)scale; op.p[5] = (void*)shift;
+  op.i[HR_BN_BWD_REDUCE_I_DTYPE] = dtype; op.i[HR_BN_BWD_REDUCE_I_N] = N; op.i[HR_BN_BWD_REDUCE_I_H] = H;
+  op.i[HR_BN_BWD_REDUCE_I_W] = W; op.i[HR_BN_BWD_REDUCE_I_C] = C; op.i[HR_BN_BWD_REDUCE_I_SH] = sh;
+  op.i[HR_BN_BWD_REDUCE_I_INNER_RELU] = inner_relu;
+  op.p[HR_BN_BWD_REDUCE_P_PARTIALS] = partials; op.p[HR_BN_BWD_REDUCE_P_G] = (void*)g;
+  op.p[HR_BN_BWD_REDUCE_P_MASK] = (void*)mask_out; op.p[HR_BN_BWD_REDUCE_P_Y] = (void*)y;
+  op.p[HR_BN_BWD_REDUCE_P_SCALE] = (void*)scale; op.p[HR_BN_BWD_REDUCE_P_SHIFT] = (void*)shift;
   return hr_launch_bn_bwd_reduce(op, (hipStream_t)stream);
 }
 
@@ -286,18 +298,22 @@ extern "C" int hrnet_bn_bwd_finalize(const float* partials, int blocks, int C, f
                                      float* dgamma, float* dbeta, float* coef, int accumulate,
                                      hr_stream_t stream) {
   OP_BEGIN(HR_OP_BN_BWD_FINALIZE);
-  op.i[0] = blocks; op.i[1] = C; op.i[2] = accumulate;
-  op.f[0] = count;
-  op.p[0] = (void*)partials; op.p[1] = (void*)gamma; op.p[2] = (void*)save_mean;
-  op.p[3] = (void*)save_invstd; op.p[4] = dgamma; op.p[5] = dbeta; op.p[6] = coef;
+  op.i[HR_BN_BWD_FINALIZE_I_BLOCKS] = blocks; op.i[HR_BN_BWD_FINALIZE_I_C] = C;
+  op.i[HR_BN_BWD_FINALIZE_I_ACCUMULATE] = accumulate;
+  op.f[HR_BN_BWD_FINALIZE_F_COUNT] = count;
+  op.p[HR_BN_BWD_FINALIZE_P_PARTIALS] = (void*)partials; op.p[HR_BN_BWD_FINALIZE_P_GAMMA] = (void*)gamma;
+  op.p[HR_BN_BWD_FINALIZE_P_SAVE_MEAN] = (void*)save_mean;
+  op.p[HR_BN_BWD_FINALIZE_P_SAVE_INVSTD] = (void*)save_invstd; op.p[HR_BN_BWD_FINALIZE_P_DGAMMA] = dgamma;
+  op.p[HR_BN_BWD_FINALIZE_P_DBETA] = dbeta; op.p[HR_BN_BWD_FINALIZE_P_COEF] = coef;
   return hr_launch_bn_bwd_finalize(op, (hipStream_t)stream);
 }
 
 static void fill_cat(HrOp& op, int dtype, const int* hs, const int* ws, const int* cs, int nbr, int N,
                      int H, int W) {
-  op.i[0] = dtype; op.i[1] = nbr; op.i[2] = N; op.i[3] = H; op.i[4] = W;
+  op.i[HR_CAT_I_DTYPE] = dtype; op.i[HR_CAT_I_NBR] = nbr; op.i[HR_CAT_I_N] = N; op.i[HR_CAT_I_H] = H;
+  op.i[HR_CAT_I_W] = W;
   for (int k = 0; k < nbr && k < 4; ++k) {
-    op.i[5 + k] = hs[k]; op.i[9 + k] = ws[k]; op.i[13 + k] = cs[k];
+    op.i[HR_CAT_I_HS0 + k] = hs[k]; op.i[HR_CAT_I_WS0 + k] = ws[k]; op.i[HR_CAT_I_CS0 + k] = cs[k];
   }
 }
 
@@ -307,9 +323,9 @@ extern "C" int hrnet_bilinear_cat(int dtype, void* cat, const void* const* xs, c
   OP_BEGIN(HR_OP_BILINEAR_CAT);
   HR_REQUIRE(nbr >= 1 && nbr <= 4 && xs && hs && ws && cs, "bilinear_cat: args");
   fill_cat(op, dtype, hs, ws, cs, nbr, N, H, W);
-  op.f[0] = align_corners ? 1.f : 0.f;
-  op.p[0] = cat;
-  for (int k = 0; k < nbr; ++k) op.p[1 + k] = (void*)xs[k];
+  op.f[HR_CAT_F_ALIGN] = align_corners ? 1.f : 0.f;
+  op.p[HR_CAT_P_CAT] = cat;
+  for (int k = 0; k < nbr; ++k) op.p[HR_CAT_P_X0 + k] = (void*)xs[k];
   return hr_launch_bilinear_cat(op, (hipStream_t)stream);
 }
 
@@ -319,10 +335,10 @@ extern "C" int hrnet_bilinear_cat_bwd(int dtype, const void* dcat, void* const* 
   OP_BEGIN(HR_OP_BILINEAR_CAT_BWD);
   HR_REQUIRE(nbr >= 1 && nbr <= 4 && dxs && hs && ws && cs, "bilinear_cat_bwd: args");
   fill_cat(op, dtype, hs, ws, cs, nbr, N, H, W);
-  op.f[0] = align_corners ? 1.f : 0.f;
-  op.i[17] = accumulate;
-  op.p[0] = (void*)dcat;
-  for (int k = 0; k < nbr; ++k) op.p[1 + k] = dxs[k];
+  op.f[HR_CAT_F_ALIGN] = align_corners ? 1.f : 0.f;
+  op.i[HR_CAT_I_ACCUMULATE] = accumulate;
+  op.p[HR_CAT_P_CAT] = (void*)dcat;
+  for (int k = 0; k < nbr; ++k) op.p[HR_CAT_P_X0 + k] = dxs[k];
   return hr_launch_bilinear_cat_bwd(op, (hipStream_t)stream);
 }
 
@@ -331,13 +347,15 @@ extern "C" int hrnet_head_mix(int dtype, const void* x0, const void* w0, const f
                               int W, int C0, int Cout, int align_corners, hr_stream_t stream) {
   OP_BEGIN(HR_OP_HEAD_MIX);
   HR_REQUIRE(nup >= 0 && nup <= 3 && (nup == 0 || (ts && hs && ws)), "head_mix: args");
-  const int iv[8] = {dtype, N, H, W, C0, Cout, nup, align_corners};
-  memcpy(op.i, iv, sizeof(iv));
-  op.i[14] = rows_mode;
-  op.p[0] = (void*)x0; op.p[1] = (void*)w0; op.p[2] = (void*)bias; op.p[3] = y; op.p[4] = stats;
+  op.i[HR_HEAD_MIX_I_DTYPE] = dtype; op.i[HR_HEAD_MIX_I_N] = N; op.i[HR_HEAD_MIX_I_H] = H;
+  op.i[HR_HEAD_MIX_I_W] = W; op.i[HR_HEAD_MIX_I_C0] = C0; op.i[HR_HEAD_MIX_I_COUT] = Cout;
+  op.i[HR_HEAD_MIX_I_NUP] = nup; op.i[HR_HEAD_MIX_I_ALIGN] = align_corners;
+  op.i[HR_HEAD_MIX_I_ROWS_MODE] = rows_mode;
+  op.p[HR_HEAD_MIX_P_X0] = (void*)x0; op.p[HR_HEAD_MIX_P_W0] = (void*)w0; op.p[HR_HEAD_MIX_P_BIAS] = (void*)bias;
+  op.p[HR_HEAD_MIX_P_Y] = y; op.p[HR_HEAD_MIX_P_STATS] = stats;
   for (int k = 0; k < nup; ++k) {
-    op.i[8 + 2 * k] = hs[k]; op.i[9 + 2 * k] = ws[k];
-    op.p[5 + k] = (void*)ts[k];
+    op.i[HR_HEAD_MIX_I_UP_H1 + 2 * k] = hs[k]; op.i[HR_HEAD_MIX_I_UP_W1 + 2 * k] = ws[k];
+    op.p[HR_HEAD_MIX_P_T1 + k] = (void*)ts[k];
   }
   return hr_launch_head_mix(op, (hipStream_t)stream);
 }
@@ -347,13 +365,14 @@ extern "C" int hrnet_upsample_bilinear_t(int dtype, const void* g, void* const* 
                                          hr_stream_t stream) {
   OP_BEGIN(HR_OP_UPSAMPLE_T);
   HR_REQUIRE(nout >= 1 && nout <= 3 && outs && hs && ws, "upsample_t: args");
-  const int iv[7] = {dtype, N, H, W, C, nout, align_corners};
-  memcpy(op.i, iv, sizeof(iv));
-  op.i[13] = streamed;
-  op.p[0] = (void*)g;
+  op.i[HR_UPSAMPLE_T_I_DTYPE] = dtype; op.i[HR_UPSAMPLE_T_I_N] = N; op.i[HR_UPSAMPLE_T_I_H] = H;
+  op.i[HR_UPSAMPLE_T_I_W] = W; op.i[HR_UPSAMPLE_T_I_C] = C; op.i[HR_UPSAMPLE_T_I_NOUT] = nout;
+  op.i[HR_UPSAMPLE_T_I_ALIGN] = align_corners;
+  op.i[HR_UPSAMPLE_T_I_STREAMED] = streamed;
+  op.p[HR_UPSAMPLE_T_P_G] = (void*)g;
   for (int k = 0; k < nout; ++k) {
-    op.p[1 + k] = outs[k];
-    op.i[7 + 2 * k] = hs[k]; op.i[8 + 2 * k] = ws[k];
+    op.p[HR_UPSAMPLE_T_P_OUT1 + k] = outs[k];
+    op.i[HR_UPSAMPLE_T_I_OUT_H1 + 2 * k] = hs[k]; op.i[HR_UPSAMPLE_T_I_OUT_W1 + 2 * k] = ws[k];
   }
   return hr_launch_upsample_t(op, (hipStream_t)stream);
 }
@@ -362,53 +381,56 @@ extern "C" int hrnet_head_bwd(int dtype, int mode, const void* dy, const void* w
                               const float* bn_scale, const float* bn_shift, const float* coef, int inner_relu, int N,
                               int H, int W, int K, int Cout, hr_stream_t stream) {
   OP_BEGIN(HR_OP_HEAD_BWD);
-  const int iv[8] = {dtype, N, H, W, K, Cout, mode, inner_relu};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)dy; op.p[1] = (void*)wT; op.p[2] = (void*)y; op.p[3] = out;
-  op.p[4] = (void*)bn_scale; op.p[5] = (void*)bn_shift; op.p[6] = (void*)coef;
+  op.i[HR_HEAD_BWD_I_DTYPE] = dtype; op.i[HR_HEAD_BWD_I_N] = N; op.i[HR_HEAD_BWD_I_H] = H;
+  op.i[HR_HEAD_BWD_I_W] = W; op.i[HR_HEAD_BWD_I_K] = K; op.i[HR_HEAD_BWD_I_COUT] = Cout;
+  op.i[HR_HEAD_BWD_I_MODE] = mode; op.i[HR_HEAD_BWD_I_INNER_RELU] = inner_relu;
+  op.p[HR_HEAD_BWD_P_DY] = (void*)dy; op.p[HR_HEAD_BWD_P_WT] = (void*)wT; op.p[HR_HEAD_BWD_P_Y] = (void*)y;
+  op.p[HR_HEAD_BWD_P_OUT] = out;
+  op.p[HR_HEAD_BWD_P_BN_SCALE] = (void*)bn_scale; op.p[HR_HEAD_BWD_P_BN_SHIFT] = (void*)bn_shift;
+  op.p[HR_HEAD_BWD_P_COEF] = (void*)coef;
   return hr_launch_head_bwd(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_im2col_stem(int dtype, const float* img_nchw, void* cols, int N, int C, int H, int W,
                                  int Ho, int Wo, int Kpad, hr_stream_t stream) {
   OP_BEGIN(HR_OP_IM2COL_STEM);
-  const int iv[8] = {dtype, N, C, H, W, Ho, Wo, Kpad};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)img_nchw; op.p[1] = cols;
+  op.i[HR_IM2COL_I_DTYPE] = dtype; op.i[HR_IM2COL_I_N] = N; op.i[HR_IM2COL_I_C] = C; op.i[HR_IM2COL_I_H] = H;
+  op.i[HR_IM2COL_I_W] = W; op.i[HR_IM2COL_I_HO] = Ho; op.i[HR_IM2COL_I_WO] = Wo; op.i[HR_IM2COL_I_KPAD] = Kpad;
+  op.p[HR_IM2COL_P_IMG] = (void*)img_nchw; op.p[HR_IM2COL_P_COLS] = cols;
   return hr_launch_im2col_stem(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_nhwc_to_nchw(int dtype, const void* src, float* dst, int N, int H, int W, int Cp,
                                   int C, hr_stream_t stream) {
   OP_BEGIN(HR_OP_NHWC_TO_NCHW);
-  const int iv[6] = {dtype, N, H, W, Cp, C};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)src; op.p[1] = dst;
+  op.i[HR_LAYOUT_I_DTYPE] = dtype; op.i[HR_LAYOUT_I_N] = N; op.i[HR_LAYOUT_I_H] = H; op.i[HR_LAYOUT_I_W] = W;
+  op.i[HR_LAYOUT_I_CP] = Cp; op.i[HR_LAYOUT_I_C] = C;
+  op.p[HR_LAYOUT_P_SRC] = (void*)src; op.p[HR_LAYOUT_P_DST] = dst;
   return hr_launch_nhwc_to_nchw(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_nchw_to_nhwc(int dtype, const float* src, void* dst, int N, int H, int W, int Cp,
                                   int C, hr_stream_t stream) {
   OP_BEGIN(HR_OP_NCHW_TO_NHWC);
-  const int iv[6] = {dtype, N, H, W, Cp, C};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)src; op.p[1] = dst;
+  op.i[HR_LAYOUT_I_DTYPE] = dtype; op.i[HR_LAYOUT_I_N] = N; op.i[HR_LAYOUT_I_H] = H; op.i[HR_LAYOUT_I_W] = W;
+  op.i[HR_LAYOUT_I_CP] = Cp; op.i[HR_LAYOUT_I_C] = C;
+  op.p[HR_LAYOUT_P_SRC] = (void*)src; op.p[HR_LAYOUT_P_DST] = dst;
   return hr_launch_nchw_to_nhwc(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_bias_grad(int dtype, const void* dy, float* dbias, float* scratch, int pixels, int Cp,
                                int C, int accumulate, hr_stream_t stream) {
   OP_BEGIN(HR_OP_BIAS_GRAD);
-  const int iv[5] = {dtype, pixels, Cp, C, accumulate};
-  memcpy(op.i, iv, sizeof(iv));
-  op.p[0] = (void*)dy; op.p[1] = dbias; op.p[2] = scratch;
+  op.i[HR_BIAS_GRAD_I_DTYPE] = dtype; op.i[HR_BIAS_GRAD_I_PIXELS] = pixels; op.i[HR_BIAS_GRAD_I_CP] = Cp;
+  op.i[HR_BIAS_GRAD_I_C] = C; op.i[HR_BIAS_GRAD_I_ACCUMULATE] = accumulate;
+  op.p[HR_BIAS_GRAD_P_DY] = (void*)dy; op.p[HR_BIAS_GRAD_P_DBIAS] = dbias; op.p[HR_BIAS_GRAD_P_SCRATCH] = scratch;
   return hr_launch_bias_grad(op, (hipStream_t)stream);
 }
 
 extern "C" int hrnet_fill_zero(void* p, int64_t bytes, hr_stream_t stream) {
   OP_BEGIN(HR_OP_FILL);
-  op.i[0] = (int32_t)(uint32_t)(bytes & 0xffffffffLL);
-  op.i[1] = (int32_t)(uint32_t)((uint64_t)bytes >> 32);
-  op.p[0] = p;
+  op.i[HR_FILL_I_BYTES_LO] = (int32_t)(uint32_t)(bytes & 0xffffffffLL);
+  op.i[HR_FILL_I_BYTES_HI] = (int32_t)(uint32_t)((uint64_t)bytes >> 32);
+  op.p[HR_FILL_P_DST] = p;
   return hr_launch_fill(op, (hipStream_t)stream);
 }

@@ -946,10 +946,16 @@ static int bwd_fused_launch(int dtype, const void* dz, const void* y, const floa
 }
 
 int hr_launch_bwd_fused(const HrOp& op, hipStream_t s) {
-  // p[12]: HOST pointer to a HrBnBwdRef (kept alive by the plan), or NULL; i[8] = 1: p[11] is the OIHW gradient the
-  // weight-gradient tiles are ADDED to (float atomics), i[9], i[10] its real Cout, Cin
-  return bwd_fused_launch(op.i[0], op.p[0], op.p[1], (const float*)op.p[2], (const HrBnBwdRef*)op.p[12], op.p[3],
-                          (const float*)op.p[4], (const float*)op.p[5], op.i[6], op.p[6], op.p[7], op.p[8], op.i[7],
-                          (float*)op.p[9], op.p[10], (float*)op.p[11], op.i[1], op.i[2], op.i[3], op.i[4], op.i[5],
-                          op.i[8], op.i[9], op.i[10], (hr_stream_t)s);
+  // BNREF: HOST pointer to a HrBnBwdRef (kept alive by the plan), or NULL; ATOMIC = 1: SLABS is the OIHW gradient the
+  // weight-gradient tiles are ADDED to (float atomics), COUT_REAL, CIN_REAL its real Cout, Cin
+  return bwd_fused_launch(op.i[HR_BWD_FUSED_I_DTYPE], op.p[HR_BWD_FUSED_P_DZ], op.p[HR_BWD_FUSED_P_Y],
+                          (const float*)op.p[HR_BWD_FUSED_P_COEF], (const HrBnBwdRef*)op.p[HR_BWD_FUSED_P_BNREF],
+                          op.p[HR_BWD_FUSED_P_X], (const float*)op.p[HR_BWD_FUSED_P_IN_SCALE],
+                          (const float*)op.p[HR_BWD_FUSED_P_IN_SHIFT], op.i[HR_BWD_FUSED_I_IN_RELU],
+                          op.p[HR_BWD_FUSED_P_WT], op.p[HR_BWD_FUSED_P_DX], op.p[HR_BWD_FUSED_P_ADDEND],
+                          op.i[HR_BWD_FUSED_I_MASK_OUT], (float*)op.p[HR_BWD_FUSED_P_ROWS], op.p[HR_BWD_FUSED_P_BS_Y],
+                          (float*)op.p[HR_BWD_FUSED_P_SLABS], op.i[HR_BWD_FUSED_I_N], op.i[HR_BWD_FUSED_I_H],
+                          op.i[HR_BWD_FUSED_I_W], op.i[HR_BWD_FUSED_I_CIN], op.i[HR_BWD_FUSED_I_COUT],
+                          op.i[HR_BWD_FUSED_I_ATOMIC], op.i[HR_BWD_FUSED_I_COUT_REAL], op.i[HR_BWD_FUSED_I_CIN_REAL],
+                          (hr_stream_t)s);
 }

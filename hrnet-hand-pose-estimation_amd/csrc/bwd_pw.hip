@@ -464,13 +464,19 @@ static int bwd_pw_launch(int dtype, const void* dz, const void* y, const float* 
   return hr_check_launch("conv1x1_bwd_fused");
 }
 
-// op slots as OP_BWD_FUSED (p[0..11] = dz,y,coef,x,scale,shift,wT,dx,addend,rows,bs_y,slabs;
-// i[0..7] = dtype,N,H,W,Cin,Cout,in_relu,mask_out)
+// HR_OP_BWD_PW takes the slots of HR_OP_BWD_FUSED (pixels = N * H * W). BNREF: HOST pointer to a HrBnBwdRef (kept alive
+// by the plan), or NULL; ATOMIC = 1: SLABS is the [Cout][Cin] gradient the weight-gradient tiles are ADDED to (float
+// atomics; COUT_REAL, CIN_REAL = its real Cout, Cin: must equal the tensors')
 int hr_launch_bwd_pw(const HrOp& op, hipStream_t s) {
-  // p[12]: HOST pointer to a HrBnBwdRef (kept alive by the plan), or NULL; i[8] = 1: p[11] is the [Cout][Cin] gradient
-  // the weight-gradient tiles are ADDED to (float atomics; i[9], i[10] = its real Cout, Cin: must equal the tensors')
-  return bwd_pw_launch(op.i[0], op.p[0], op.p[1], (const float*)op.p[2], (const HrBnBwdRef*)op.p[12], op.p[3],
-                       (const float*)op.p[4], (const float*)op.p[5], op.i[6], op.p[6], op.p[7], op.p[8], op.i[7],
-                       (float*)op.p[9], op.p[10], (float*)op.p[11], (long long)op.i[1] * op.i[2] * op.i[3], op.i[4],
-                       op.i[5], (op.i[8] && op.i[9] == op.i[5] && op.i[10] == op.i[4]) ? 1 : (op.i[8] ? -1 : 0), (hr_stream_t)s);
+  const int Cin = op.i[HR_BWD_FUSED_I_CIN], Cout = op.i[HR_BWD_FUSED_I_COUT];
+  const bool unpadded = op.i[HR_BWD_FUSED_I_COUT_REAL] == Cout && op.i[HR_BWD_FUSED_I_CIN_REAL] == Cin;
+  return bwd_pw_launch(op.i[HR_BWD_FUSED_I_DTYPE], op.p[HR_BWD_FUSED_P_DZ], op.p[HR_BWD_FUSED_P_Y],
+                       (const float*)op.p[HR_BWD_FUSED_P_COEF], (const HrBnBwdRef*)op.p[HR_BWD_FUSED_P_BNREF],
+                       op.p[HR_BWD_FUSED_P_X], (const float*)op.p[HR_BWD_FUSED_P_IN_SCALE],
+                       (const float*)op.p[HR_BWD_FUSED_P_IN_SHIFT], op.i[HR_BWD_FUSED_I_IN_RELU],
+                       op.p[HR_BWD_FUSED_P_WT], op.p[HR_BWD_FUSED_P_DX], op.p[HR_BWD_FUSED_P_ADDEND],
+                       op.i[HR_BWD_FUSED_I_MASK_OUT], (float*)op.p[HR_BWD_FUSED_P_ROWS], op.p[HR_BWD_FUSED_P_BS_Y],
+                       (float*)op.p[HR_BWD_FUSED_P_SLABS],
+                       (long long)op.i[HR_BWD_FUSED_I_N] * op.i[HR_BWD_FUSED_I_H] * op.i[HR_BWD_FUSED_I_W], Cin, Cout,
+                       op.i[HR_BWD_FUSED_I_ATOMIC] ? (unpadded ? 1 : -1) : 0, (hr_stream_t)s);
 }

@@ -67,7 +67,7 @@ extern "C" int hrnet_conv_rows_bwdstats(int dtype, int N, int Ho, int Wo, int Ci
   return hrnet_conv_tiles_bwdstats(N, Ho, Wo, Cout, ks, stride);
 }
 
-// Which kernel family a recorded backward-statistics launch is bound to (HrOp.i[17] of HR_OP_CONV): 2 = the LDS-ring
+// Which kernel family a recorded backward-statistics launch is bound to (HR_CONV_I_ROUTE of HR_OP_CONV): 2 = the LDS-ring
 // pipeline, 1 = the tile-walking body. A plan sizes the launch's rows buffer (and the finalize launch's row count) from
 // hrnet_conv_rows_bwdstats when it is recorded; hrnet_conv_ring_enable() is a process-wide run-time switch, so the
 // op carries the decision and hr_launch_conv() follows it - or fails - instead of deciding again (0: decide at launch,
@@ -87,9 +87,10 @@ extern "C" int hrnet_conv_tile_walk(int N, int Ho, int Wo, int Cout, int ks, int
 }
 
 int hr_launch_conv(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], Cin = op.i[4], Ho = op.i[5],
-            Wo = op.i[6], Cout = op.i[7], ks = op.i[8], upz = op.i[10];
-  int stride = op.i[9];
+  const int dtype = op.i[HR_CONV_I_DTYPE], N = op.i[HR_CONV_I_N], H = op.i[HR_CONV_I_H], W = op.i[HR_CONV_I_W],
+            Cin = op.i[HR_CONV_I_CIN], Ho = op.i[HR_CONV_I_HO], Wo = op.i[HR_CONV_I_WO], Cout = op.i[HR_CONV_I_COUT],
+            ks = op.i[HR_CONV_I_KS], upz = op.i[HR_CONV_I_UPZ];
+  int stride = op.i[HR_CONV_I_STRIDE];
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "conv2d: bad dtype %d", dtype);
   HR_REQUIRE(ks == 1 || ks == 3, "conv2d: kernel size %d not supported (1 or 3)", ks);
   HR_REQUIRE(stride == 1 || stride == 2, "conv2d: stride %d not supported", stride);
@@ -97,53 +98,55 @@ int hr_launch_conv(const HrOp& op, hipStream_t s) {
   HR_REQUIRE(Cin % (dtype == HR_F32 ? 4 : 8) == 0, "conv2d: Cin=%d not a 16-byte multiple", Cin);
   HR_REQUIRE(Cout % 16 == 0, "conv2d: Cout=%d must be a multiple of 16 (pad the tensor)", Cout);
   HR_REQUIRE(N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "conv2d: empty shape");
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[5], "conv2d: null tensor pointer");
-  HR_REQUIRE((op.p[2] == nullptr) == (op.p[3] == nullptr), "conv2d: scale/shift must come together");
+  HR_REQUIRE(op.p[HR_CONV_P_X] && op.p[HR_CONV_P_WGT] && op.p[HR_CONV_P_Y], "conv2d: null tensor pointer");
+  HR_REQUIRE((op.p[HR_CONV_P_IN_SCALE] == nullptr) == (op.p[HR_CONV_P_IN_SHIFT] == nullptr),
+             "conv2d: scale/shift must come together");
   ConvArgs a = {};
-  a.bs_store_masked = op.i[14];
-  a.in_dy = op.i[15]; a.in_dx = op.i[16];
-  HR_REQUIRE((a.in_dy == 0 && a.in_dx == 0) || (ks == 1 && stride == 1 && !upz && !op.p[7]),
+  a.bs_store_masked = op.i[HR_CONV_I_BS_STORE_MASKED];
+  a.in_dy = op.i[HR_CONV_I_IN_DY]; a.in_dx = op.i[HR_CONV_I_IN_DX];
+  HR_REQUIRE((a.in_dy == 0 && a.in_dx == 0) || (ks == 1 && stride == 1 && !upz && !op.p[HR_CONV_P_BS_Y]),
              "conv2d: a displaced input window belongs to a 1x1 stride-1 launch");
-  a.x = (const char*)op.p[0];
-  a.w = (const char*)op.p[1];
-  a.in_scale = (const float*)op.p[2];
-  a.in_shift = (const float*)op.p[3];
-  a.bias = (const float*)op.p[4];
-  a.y = (char*)op.p[5];
-  a.stats = (float*)op.p[6];
-  a.bs_y = (const char*)op.p[7];
-  a.bs_mask = (const char*)op.p[8];
-  a.bs_scale = (const float*)op.p[9];
-  a.bs_shift = (const float*)op.p[10];
-  a.in_sums = (const float*)op.p[11];
-  a.in_gamma = (const float*)op.p[12];
-  a.in_beta = (const float*)op.p[13];
-  a.in_inv_count = op.f[0];
-  a.in_eps = op.f[1];
-  a.stats_atomic = op.i[13];
+  a.x = (const char*)op.p[HR_CONV_P_X];
+  a.w = (const char*)op.p[HR_CONV_P_WGT];
+  a.in_scale = (const float*)op.p[HR_CONV_P_IN_SCALE];
+  a.in_shift = (const float*)op.p[HR_CONV_P_IN_SHIFT];
+  a.bias = (const float*)op.p[HR_CONV_P_BIAS];
+  a.y = (char*)op.p[HR_CONV_P_Y];
+  a.stats = (float*)op.p[HR_CONV_P_STATS];
+  a.bs_y = (const char*)op.p[HR_CONV_P_BS_Y];
+  a.bs_mask = (const char*)op.p[HR_CONV_P_BS_MASK];
+  a.bs_scale = (const float*)op.p[HR_CONV_P_BS_SCALE];
+  a.bs_shift = (const float*)op.p[HR_CONV_P_BS_SHIFT];
+  a.in_sums = (const float*)op.p[HR_CONV_P_IN_SUMS];
+  a.in_gamma = (const float*)op.p[HR_CONV_P_IN_GAMMA];
+  a.in_beta = (const float*)op.p[HR_CONV_P_IN_BETA];
+  a.in_inv_count = op.f[HR_CONV_F_IN_INV_COUNT];
+  a.in_eps = op.f[HR_CONV_F_IN_EPS];
+  a.stats_atomic = op.i[HR_CONV_I_STATS_ATOMIC];
   HR_REQUIRE(!a.in_sums || (a.in_gamma && a.in_beta && !a.in_scale && Cin <= HR_CONV_MAXC && a.in_inv_count > 0.f),
              "conv2d: input batch sums need gamma/beta, no scale/shift arrays, Cin <= %d", HR_CONV_MAXC);
   HR_REQUIRE(!a.in_sums || !a.bs_y, "conv2d: batch-sum input is for forward launches");
   HR_REQUIRE(!a.bs_y || a.stats, "conv2d: backward statistics need a rows buffer");
   HR_REQUIRE(!a.bs_store_masked || a.bs_y, "conv2d: the masked store belongs to a backward-statistics launch");
-  HR_REQUIRE(!a.bs_y || (!a.in_scale && !a.bias && !op.i[11]),
+  HR_REQUIRE(!a.bs_y || (!a.in_scale && !a.bias && !op.i[HR_CONV_I_IN_RELU]),
              "conv2d: backward statistics are for input-gradient launches (no input affine / ReLU / bias)");
   HR_REQUIRE((a.bs_scale == nullptr) == (a.bs_shift == nullptr), "conv2d: mask scale/shift must come together");
   a.N = N; a.H = H; a.W = W; a.Cin = Cin;
   a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
-  a.in_relu = op.i[11]; a.upz = upz; a.accumulate = op.i[12];
-  const int mode = conv_mode(a, op.i[11] != 0);
+  a.in_relu = op.i[HR_CONV_I_IN_RELU]; a.upz = upz; a.accumulate = op.i[HR_CONV_I_ACCUMULATE];
+  const int mode = conv_mode(a, op.i[HR_CONV_I_IN_RELU] != 0);
   HR_REQUIRE(!a.in_sums || mode == CONV_FWD || mode == CONV_FWDB,
              "conv2d: batch-sum input needs a forward launch that writes statistics or adds a bias");
   // the branch 3x3 convolutions: LDS-ring pipeline (conv_ring.hip)
-  const int route = op.i[17];
+  const int route = op.i[HR_CONV_I_ROUTE];
   HR_REQUIRE(route >= 0 && route <= 2, "conv2d: bad route %d", route);
-  const int rs = route == 1 ? 0 : ring_serves(a, dtype, ks, op.i[9], mode, op.i[11] != 0);
+  const int rs = route == 1 ? 0 : ring_serves(a, dtype, ks, op.i[HR_CONV_I_STRIDE], mode, op.i[HR_CONV_I_IN_RELU] != 0);
   HR_REQUIRE(route != 2 || rs, "conv2d: the op was recorded for the LDS-ring kernel, which does not serve it now "
              "(hrnet_conv_ring_enable() changed after the plan was recorded: record the plan again)");
-  if (rs) return launch_ring(a, op.i[11], s);
+  if (rs) return launch_ring(a, op.i[HR_CONV_I_IN_RELU], s);
   // the GEMM-shaped head layer (and its input gradient): every output channel of a pixel block in one workgroup
-  if (ks == 1 && stride == 1 && !upz && !a.accumulate && !a.bs_y && !a.in_scale && !a.in_sums && !op.i[11] &&
+  if (ks == 1 && stride == 1 && !upz && !a.accumulate && !a.bs_y && !a.in_scale && !a.in_sums &&
+      !op.i[HR_CONV_I_IN_RELU] &&
       (!a.stats || a.stats_atomic) && !a.in_dy && !a.in_dx && hr_gemm_pw_supported(dtype, Cin, Cout))
     return hr_gemm_pw(a.x, a.w, a.bias, a.y, a.stats, (long long)N * H * W, Cin, Cout, s);
   // input gradient of a 3x3 stride-2 conv: the input-gradient bodies evaluate the four output parities
@@ -161,7 +164,7 @@ int hr_launch_conv(const HrOp& op, hipStream_t s) {
                "conv2d: output %dx%d does not match input %dx%d ks=%d stride=%d", Ho, Wo, H, W, ks, stride);
     a.Hz = H; a.Wz = W;
   }
-  const TileChoice tc = choose_tile(N, Ho, Wo, Cout, ks, op.i[9], op.p[7] != nullptr, s2d);
+  const TileChoice tc = choose_tile(N, Ho, Wo, Cout, ks, op.i[HR_CONV_I_STRIDE], op.p[HR_CONV_P_BS_Y] != nullptr, s2d);
   a.tiles_y = (Ho + tc.th - 1) / tc.th;
   a.tiles_x = (Wo + tc.tw - 1) / tc.tw;
   a.total_tiles = N * a.tiles_y * a.tiles_x;
@@ -182,30 +185,31 @@ int hr_launch_conv(const HrOp& op, hipStream_t s) {
   }
 }
 
-// HR_OP_CONV_SUM: i = dtype,N,H,W,Cin,Cout,ks,stats_atomic; f = 1/count, eps;
-// p = x, w, in_scale, in_shift, in_sums, in_gamma, in_beta, y, stats, x2, side
+// HR_OP_CONV_SUM (slots: HR_CONV_SUM_*)
 int hr_launch_conv_sum(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], Cin = op.i[4], Cout = op.i[5], ks = op.i[6];
+  const int dtype = op.i[HR_CONV_SUM_I_DTYPE], N = op.i[HR_CONV_SUM_I_N], H = op.i[HR_CONV_SUM_I_H],
+            W = op.i[HR_CONV_SUM_I_W], Cin = op.i[HR_CONV_SUM_I_CIN], Cout = op.i[HR_CONV_SUM_I_COUT],
+            ks = op.i[HR_CONV_SUM_I_KS];
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "conv2d_sum: bad dtype %d", dtype);
   HR_REQUIRE(ks == 1 || ks == 3, "conv2d_sum: kernel size %d", ks);
   HR_REQUIRE(N > 0 && H > 0 && W > 0, "conv2d_sum: empty shape");
   HR_REQUIRE(Cin % (dtype == HR_F32 ? 4 : 8) == 0 && Cout % 16 == 0, "conv2d_sum: channel counts (Cin=%d Cout=%d)", Cin, Cout);
   HR_REQUIRE((double)H * W * (Cin > Cout ? Cin : Cout) * 4.0 < 2147483648.0, "conv2d_sum: one image exceeds 2 GiB");
   ConvArgs a = {};
-  a.x = (const char*)op.p[0];
-  a.w = (const char*)op.p[1];
-  a.in_scale = (const float*)op.p[2];
-  a.in_shift = (const float*)op.p[3];
-  a.in_sums = (const float*)op.p[4];
-  a.in_gamma = (const float*)op.p[5];
-  a.in_beta = (const float*)op.p[6];
-  a.y = (char*)op.p[7];
-  a.stats = (float*)op.p[8];
-  a.x2 = (const char*)op.p[9];
-  a.side = (char*)op.p[10];
-  a.in_inv_count = op.f[0];
-  a.in_eps = op.f[1];
-  a.stats_atomic = op.i[7];
+  a.x = (const char*)op.p[HR_CONV_SUM_P_X];
+  a.w = (const char*)op.p[HR_CONV_SUM_P_WGT];
+  a.in_scale = (const float*)op.p[HR_CONV_SUM_P_IN_SCALE];
+  a.in_shift = (const float*)op.p[HR_CONV_SUM_P_IN_SHIFT];
+  a.in_sums = (const float*)op.p[HR_CONV_SUM_P_IN_SUMS];
+  a.in_gamma = (const float*)op.p[HR_CONV_SUM_P_IN_GAMMA];
+  a.in_beta = (const float*)op.p[HR_CONV_SUM_P_IN_BETA];
+  a.y = (char*)op.p[HR_CONV_SUM_P_Y];
+  a.stats = (float*)op.p[HR_CONV_SUM_P_STATS];
+  a.x2 = (const char*)op.p[HR_CONV_SUM_P_X2];
+  a.side = (char*)op.p[HR_CONV_SUM_P_SIDE];
+  a.in_inv_count = op.f[HR_CONV_SUM_F_IN_INV_COUNT];
+  a.in_eps = op.f[HR_CONV_SUM_F_IN_EPS];
+  a.stats_atomic = op.i[HR_CONV_SUM_I_STATS_ATOMIC];
   HR_REQUIRE(a.x && a.w && a.y && a.x2 && a.side, "conv2d_sum: null pointer");
   HR_REQUIRE((a.in_scale != nullptr) == (a.in_shift != nullptr), "conv2d_sum: scale/shift must come together");
   HR_REQUIRE((a.in_scale != nullptr) != (a.in_sums != nullptr), "conv2d_sum: the BatchNorm term needs scale/shift OR batch sums");
@@ -238,12 +242,15 @@ extern "C" int hrnet_conv2d_sum(int dtype, const void* x, const void* x2, const 
                                 hr_stream_t stream) {
   HrOp op = {};
   op.kind = HR_OP_CONV_SUM;
-  const int iv[8] = {dtype, N, H, W, Cin, Cout, ks, stats_atomic};
-  for (int k = 0; k < 8; ++k) op.i[k] = iv[k];
-  op.f[0] = in_inv_count; op.f[1] = in_eps;
-  op.p[0] = (void*)x; op.p[1] = (void*)w; op.p[2] = (void*)in_scale; op.p[3] = (void*)in_shift;
-  op.p[4] = (void*)in_sums; op.p[5] = (void*)in_gamma; op.p[6] = (void*)in_beta; op.p[7] = y; op.p[8] = stats;
-  op.p[9] = (void*)x2; op.p[10] = side;
+  op.i[HR_CONV_SUM_I_DTYPE] = dtype; op.i[HR_CONV_SUM_I_N] = N; op.i[HR_CONV_SUM_I_H] = H;
+  op.i[HR_CONV_SUM_I_W] = W; op.i[HR_CONV_SUM_I_CIN] = Cin; op.i[HR_CONV_SUM_I_COUT] = Cout;
+  op.i[HR_CONV_SUM_I_KS] = ks; op.i[HR_CONV_SUM_I_STATS_ATOMIC] = stats_atomic;
+  op.f[HR_CONV_SUM_F_IN_INV_COUNT] = in_inv_count; op.f[HR_CONV_SUM_F_IN_EPS] = in_eps;
+  op.p[HR_CONV_SUM_P_X] = (void*)x; op.p[HR_CONV_SUM_P_WGT] = (void*)w;
+  op.p[HR_CONV_SUM_P_IN_SCALE] = (void*)in_scale; op.p[HR_CONV_SUM_P_IN_SHIFT] = (void*)in_shift;
+  op.p[HR_CONV_SUM_P_IN_SUMS] = (void*)in_sums; op.p[HR_CONV_SUM_P_IN_GAMMA] = (void*)in_gamma;
+  op.p[HR_CONV_SUM_P_IN_BETA] = (void*)in_beta; op.p[HR_CONV_SUM_P_Y] = y; op.p[HR_CONV_SUM_P_STATS] = stats;
+  op.p[HR_CONV_SUM_P_X2] = (void*)x2; op.p[HR_CONV_SUM_P_SIDE] = side;
   return hr_launch_conv_sum(op, (hipStream_t)stream);
 }
 
@@ -256,13 +263,14 @@ extern "C" int hrnet_conv2d_dilated3x3(int dtype, const void* x, const void* w_t
   for (int t = 0; t < 9; ++t) {
     HrOp op = {};
     op.kind = HR_OP_CONV;
-    const int iv[13] = {dtype, N, H, W, Cin, H, W, Cout, 1, 1, 0, 0, t > 0 ? 1 : 0};
-    for (int k = 0; k < 13; ++k) op.i[k] = iv[k];
-    op.i[15] = (t / 3 - 1) * dilation;
-    op.i[16] = (t % 3 - 1) * dilation;
-    op.p[0] = (void*)x;
-    op.p[1] = (void*)((const char*)w_taps + (size_t)t * tap_stride_bytes);
-    op.p[5] = y;
+    op.i[HR_CONV_I_DTYPE] = dtype; op.i[HR_CONV_I_N] = N; op.i[HR_CONV_I_H] = H; op.i[HR_CONV_I_W] = W;
+    op.i[HR_CONV_I_CIN] = Cin; op.i[HR_CONV_I_HO] = H; op.i[HR_CONV_I_WO] = W; op.i[HR_CONV_I_COUT] = Cout;
+    op.i[HR_CONV_I_KS] = 1; op.i[HR_CONV_I_STRIDE] = 1; op.i[HR_CONV_I_ACCUMULATE] = t > 0 ? 1 : 0;
+    op.i[HR_CONV_I_IN_DY] = (t / 3 - 1) * dilation;
+    op.i[HR_CONV_I_IN_DX] = (t % 3 - 1) * dilation;
+    op.p[HR_CONV_P_X] = (void*)x;
+    op.p[HR_CONV_P_WGT] = (void*)((const char*)w_taps + (size_t)t * tap_stride_bytes);
+    op.p[HR_CONV_P_Y] = y;
     if (int e = hr_launch_conv(op, (hipStream_t)stream)) return e;
   }
   return 0;
@@ -274,10 +282,13 @@ extern "C" int hrnet_conv2d(int dtype, const void* x, const void* w, const float
                             int upz, int in_relu, int accumulate, hr_stream_t stream) {
   HrOp op = {};
   op.kind = HR_OP_CONV;
-  const int iv[13] = {dtype, N, H, W, Cin, Ho, Wo, Cout, ks, stride, upz, in_relu, accumulate};
-  for (int k = 0; k < 13; ++k) op.i[k] = iv[k];
-  op.p[0] = (void*)x; op.p[1] = (void*)w; op.p[2] = (void*)in_scale; op.p[3] = (void*)in_shift;
-  op.p[4] = (void*)bias; op.p[5] = y; op.p[6] = stats;
+  op.i[HR_CONV_I_DTYPE] = dtype; op.i[HR_CONV_I_N] = N; op.i[HR_CONV_I_H] = H; op.i[HR_CONV_I_W] = W;
+  op.i[HR_CONV_I_CIN] = Cin; op.i[HR_CONV_I_HO] = Ho; op.i[HR_CONV_I_WO] = Wo; op.i[HR_CONV_I_COUT] = Cout;
+  op.i[HR_CONV_I_KS] = ks; op.i[HR_CONV_I_STRIDE] = stride; op.i[HR_CONV_I_UPZ] = upz;
+  op.i[HR_CONV_I_IN_RELU] = in_relu; op.i[HR_CONV_I_ACCUMULATE] = accumulate;
+  op.p[HR_CONV_P_X] = (void*)x; op.p[HR_CONV_P_WGT] = (void*)w; op.p[HR_CONV_P_IN_SCALE] = (void*)in_scale;
+  op.p[HR_CONV_P_IN_SHIFT] = (void*)in_shift;
+  op.p[HR_CONV_P_BIAS] = (void*)bias; op.p[HR_CONV_P_Y] = y; op.p[HR_CONV_P_STATS] = stats;
   return hr_launch_conv(op, (hipStream_t)stream);
 }
 
@@ -287,11 +298,15 @@ extern "C" int hrnet_conv2d_bnref(int dtype, const void* x, const void* w, const
                                   int stride, int in_relu, hr_stream_t stream) {
   HrOp op = {};
   op.kind = HR_OP_CONV;
-  const int iv[14] = {dtype, N, H, W, Cin, Ho, Wo, Cout, ks, stride, 0, in_relu, 0, 1};
-  for (int k = 0; k < 14; ++k) op.i[k] = iv[k];
-  op.p[0] = (void*)x; op.p[1] = (void*)w; op.p[4] = (void*)bias; op.p[5] = y; op.p[6] = out_sums;
-  op.p[11] = (void*)in_sums; op.p[12] = (void*)in_gamma; op.p[13] = (void*)in_beta;
-  op.f[0] = in_inv_count; op.f[1] = in_eps;
+  op.i[HR_CONV_I_DTYPE] = dtype; op.i[HR_CONV_I_N] = N; op.i[HR_CONV_I_H] = H; op.i[HR_CONV_I_W] = W;
+  op.i[HR_CONV_I_CIN] = Cin; op.i[HR_CONV_I_HO] = Ho; op.i[HR_CONV_I_WO] = Wo; op.i[HR_CONV_I_COUT] = Cout;
+  op.i[HR_CONV_I_KS] = ks; op.i[HR_CONV_I_STRIDE] = stride; op.i[HR_CONV_I_IN_RELU] = in_relu;
+  op.i[HR_CONV_I_STATS_ATOMIC] = 1;
+  op.p[HR_CONV_P_X] = (void*)x; op.p[HR_CONV_P_WGT] = (void*)w; op.p[HR_CONV_P_BIAS] = (void*)bias;
+  op.p[HR_CONV_P_Y] = y; op.p[HR_CONV_P_STATS] = out_sums;
+  op.p[HR_CONV_P_IN_SUMS] = (void*)in_sums; op.p[HR_CONV_P_IN_GAMMA] = (void*)in_gamma;
+  op.p[HR_CONV_P_IN_BETA] = (void*)in_beta;
+  op.f[HR_CONV_F_IN_INV_COUNT] = in_inv_count; op.f[HR_CONV_F_IN_EPS] = in_eps;
   return hr_launch_conv(op, (hipStream_t)stream);
 }
 
@@ -301,10 +316,13 @@ extern "C" int hrnet_conv2d_bwdstats(int dtype, const void* x, const void* w, vo
                                      int Cout, int ks, int stride, int upz, int accumulate, hr_stream_t stream) {
   HrOp op = {};
   op.kind = HR_OP_CONV;
-  const int iv[13] = {dtype, N, H, W, Cin, Ho, Wo, Cout, ks, stride, upz, 0, accumulate};
-  for (int k = 0; k < 13; ++k) op.i[k] = iv[k];
-  op.p[0] = (void*)x; op.p[1] = (void*)w; op.p[5] = y; op.p[6] = stats;
-  op.p[7] = (void*)bs_y; op.p[8] = (void*)bs_mask; op.p[9] = (void*)bs_scale; op.p[10] = (void*)bs_shift;
+  op.i[HR_CONV_I_DTYPE] = dtype; op.i[HR_CONV_I_N] = N; op.i[HR_CONV_I_H] = H; op.i[HR_CONV_I_W] = W;
+  op.i[HR_CONV_I_CIN] = Cin; op.i[HR_CONV_I_HO] = Ho; op.i[HR_CONV_I_WO] = Wo; op.i[HR_CONV_I_COUT] = Cout;
+  op.i[HR_CONV_I_KS] = ks; op.i[HR_CONV_I_STRIDE] = stride; op.i[HR_CONV_I_UPZ] = upz;
+  op.i[HR_CONV_I_ACCUMULATE] = accumulate;
+  op.p[HR_CONV_P_X] = (void*)x; op.p[HR_CONV_P_WGT] = (void*)w; op.p[HR_CONV_P_Y] = y; op.p[HR_CONV_P_STATS] = stats;
+  op.p[HR_CONV_P_BS_Y] = (void*)bs_y; op.p[HR_CONV_P_BS_MASK] = (void*)bs_mask;
+  op.p[HR_CONV_P_BS_SCALE] = (void*)bs_scale; op.p[HR_CONV_P_BS_SHIFT] = (void*)bs_shift;
   HR_REQUIRE(bs_y, "conv2d_bwdstats: null bs_y");
   return hr_launch_conv(op, (hipStream_t)stream);
 }

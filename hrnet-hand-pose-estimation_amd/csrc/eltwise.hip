@@ -181,17 +181,18 @@ __global__ __launch_bounds__(256) void sum_terms_kernel(SumArgs a) {
 
 // slots of a HR_OP_SUM_TERMS op -> SumArgs (host: hr_launch_sum_terms; device: the table-driven launch)
 __host__ __device__ inline void sum_args_from_op(const HrOp& op, SumArgs& a) {
-  a.N = op.i[1]; a.Ho = op.i[2]; a.Wo = op.i[3]; a.C = op.i[4]; a.nterms = op.i[5]; a.relu_out = op.i[6];
-  a.out = (char*)op.p[0];
-  a.sums_mode = op.i[15];
+  a.N = op.i[HR_SUM_I_N]; a.Ho = op.i[HR_SUM_I_H]; a.Wo = op.i[HR_SUM_I_W]; a.C = op.i[HR_SUM_I_C];
+  a.nterms = op.i[HR_SUM_I_NTERMS]; a.relu_out = op.i[HR_SUM_I_RELU_OUT];
+  a.out = (char*)op.p[HR_SUM_P_OUT];
+  a.sums_mode = op.i[HR_SUM_I_SUMS_MODE];
   for (int t = 0; t < 4; ++t) a.inv_count[t] = op.f[t];
-  a.eps = __builtin_bit_cast(float, op.i[16]);
+  a.eps = __builtin_bit_cast(float, op.i[HR_SUM_I_EPS_BITS]);
   for (int t = 0; t < 4; ++t) {
-    a.sh[t] = op.i[7 + t];
-    a.relu[t] = op.i[11 + t];
-    a.src[t] = (const char*)op.p[1 + t];
-    a.scale[t] = (const float*)op.p[5 + t];
-    a.shift[t] = (const float*)op.p[9 + t];
+    a.sh[t] = op.i[HR_SUM_I_SH0 + t];
+    a.relu[t] = op.i[HR_SUM_I_RELU0 + t];
+    a.src[t] = (const char*)op.p[HR_SUM_P_SRC0 + t];
+    a.scale[t] = (const float*)op.p[HR_SUM_P_SCALE0 + t];
+    a.shift[t] = (const float*)op.p[HR_SUM_P_SHIFT0 + t];
   }
 }
 
@@ -572,11 +573,12 @@ __device__ __forceinline__ void pool_reduce_block(const PoolArgs& a, int bid, in
 }
 
 __host__ __device__ inline void pool_args_from_op(const HrOp& op, PoolArgs& a) {
-  // slots: i = {dtype, N, H, W, C, nlev}, p = {g, mask, y1, dz1, partials1, y2, dz2, partials2, y3, dz3, partials3}
-  a.N = op.i[1]; a.H = op.i[2]; a.W = op.i[3]; a.C = op.i[4]; a.nlev = op.i[5];
-  a.g = (const char*)op.p[0]; a.mask = (const char*)op.p[1];
+  a.N = op.i[HR_POOL_I_N]; a.H = op.i[HR_POOL_I_H]; a.W = op.i[HR_POOL_I_W]; a.C = op.i[HR_POOL_I_C];
+  a.nlev = op.i[HR_POOL_I_NLEV];
+  a.g = (const char*)op.p[HR_POOL_P_G]; a.mask = (const char*)op.p[HR_POOL_P_MASK];
   for (int l = 0; l < 3; ++l) {
-    a.y[l] = (const char*)op.p[2 + 3 * l]; a.dz[l] = (char*)op.p[3 + 3 * l]; a.partials[l] = (float*)op.p[4 + 3 * l];
+    a.y[l] = (const char*)op.p[HR_POOL_P_Y0 + 3 * l]; a.dz[l] = (char*)op.p[HR_POOL_P_DZ0 + 3 * l];
+    a.partials[l] = (float*)op.p[HR_POOL_P_PARTIALS0 + 3 * l];
   }
 }
 
@@ -637,31 +639,65 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(
 }
 
 // ---- batched launches (HR_OP_EW_TABLE): several HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE jobs of
-// one kind as ONE launch. The table holds the jobs as HrOp records in device memory (slots as for the single ops;
-// i[16] = first block of the job, i[17] = its block count); a block finds its job by binary search. The module
-// fuse layers leave a dozen such jobs on tensors of a few MB per HighResolutionModule: as launches of their own
-// they are latency, not work. Same device code as the single launches: same values bit for bit.
+// one kind as ONE launch. The table holds the jobs as HrOp records in device memory (slots as for the single ops,
+// HR_EWJOB_I_BLOCK0 = first block of the job, HR_EWJOB_I_BLOCKS = its block count); a block finds its job by binary
+// search. The module fuse layers leave a dozen such jobs on tensors of a few MB per HighResolutionModule: as launches
+// of their own they are latency, not work. Same device code as the single launches: same values bit for bit.
 __device__ __forceinline__ const HrOp& ew_table_find(const HrOp* tab, int n, int& local) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].i[16] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+    if (tab[mid].i[HR_EWJOB_I_BLOCK0] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
   }
-  local = (int)blockIdx.x - tab[lo].i[16];
+  local = (int)blockIdx.x - tab[lo].i[HR_EWJOB_I_BLOCK0];
   return tab[lo];
 }
 
-__device__ __forceinline__ GradArgs ew_grad_args(const HrOp& op, bool reduce) {
+// slots of a HR_OP_GRAD_TERM (reduce = false) or HR_OP_BN_BWD_REDUCE (reduce = true) op -> GradArgs (host: the
+// launchers below; device: the table-driven launches). The shape and the g / mask / y / scale / shift slots are the
+// same in both kinds; a reduction has no accumulate flags, no second destination and no coefficients.
+__host__ __device__ __forceinline__ GradArgs grad_args_from_op(const HrOp& op, bool reduce) {
   GradArgs a;
-  a.N = op.i[1]; a.H = op.i[2]; a.W = op.i[3]; a.C = op.i[4]; a.sh = op.i[5]; a.inner_relu = op.i[6];
-  a.accumulate = reduce ? 0 : op.i[7];
-  a.accumulate2 = reduce ? 0 : op.i[8];
-  a.dst2 = reduce ? nullptr : (char*)op.p[7];
-  a.partials = reduce ? (float*)op.p[0] : nullptr;
-  a.dst = reduce ? (char*)op.p[6] : (char*)op.p[0];      // (reduce: optional store of the pooled, masked gradient)
-  a.coef = reduce ? nullptr : (const float*)op.p[6];
-  a.g = (const char*)op.p[1]; a.mask = (const char*)op.p[2]; a.y = (const char*)op.p[3];
-  a.scale = (const float*)op.p[4]; a.shift = (const float*)op.p[5];
+  a.N = op.i[HR_GRAD_TERM_I_N]; a.H = op.i[HR_GRAD_TERM_I_H]; a.W = op.i[HR_GRAD_TERM_I_W];
+  a.C = op.i[HR_GRAD_TERM_I_C];
+  a.sh = op.i[HR_GRAD_TERM_I_SH]; a.inner_relu = op.i[HR_GRAD_TERM_I_INNER_RELU];
+  a.accumulate = reduce ? 0 : op.i[HR_GRAD_TERM_I_ACCUMULATE];
+  a.accumulate2 = reduce ? 0 : op.i[HR_GRAD_TERM_I_ACCUMULATE2];
+  a.dst2 = reduce ? nullptr : (char*)op.p[HR_GRAD_TERM_P_DST2];
+  a.partials = reduce ? (float*)op.p[HR_BN_BWD_REDUCE_P_PARTIALS] : nullptr;
+  // (reduce: optional store of the pooled, masked gradient)
+  a.dst = reduce ? (char*)op.p[HR_BN_BWD_REDUCE_P_DZ] : (char*)op.p[HR_GRAD_TERM_P_DST];
+  a.coef = reduce ? nullptr : (const float*)op.p[HR_GRAD_TERM_P_COEF];
+  a.g = (const char*)op.p[HR_GRAD_TERM_P_G]; a.mask = (const char*)op.p[HR_GRAD_TERM_P_MASK];
+  a.y = (const char*)op.p[HR_GRAD_TERM_P_Y];
+  a.scale = (const float*)op.p[HR_GRAD_TERM_P_SCALE]; a.shift = (const float*)op.p[HR_GRAD_TERM_P_SHIFT];
+  return a;
+}
+static_assert(HR_BN_BWD_REDUCE_I_N == HR_GRAD_TERM_I_N && HR_BN_BWD_REDUCE_I_H == HR_GRAD_TERM_I_H &&
+              HR_BN_BWD_REDUCE_I_W == HR_GRAD_TERM_I_W && HR_BN_BWD_REDUCE_I_C == HR_GRAD_TERM_I_C &&
+              HR_BN_BWD_REDUCE_I_SH == HR_GRAD_TERM_I_SH &&
+                  HR_BN_BWD_REDUCE_I_INNER_RELU == HR_GRAD_TERM_I_INNER_RELU &&
+              HR_BN_BWD_REDUCE_P_G == HR_GRAD_TERM_P_G && HR_BN_BWD_REDUCE_P_MASK == HR_GRAD_TERM_P_MASK &&
+              HR_BN_BWD_REDUCE_P_Y == HR_GRAD_TERM_P_Y && HR_BN_BWD_REDUCE_P_SCALE == HR_GRAD_TERM_P_SCALE &&
+              HR_BN_BWD_REDUCE_P_SHIFT == HR_GRAD_TERM_P_SHIFT, "grad_args_from_op reads both kinds");
+
+// slots of a HR_OP_BN_BWD_FINALIZE op (host: hr_launch_bn_bwd_finalize; device: the table-driven launch)
+struct BnBwdFinArgs {
+  const float *partials, *gamma, *save_mean, *save_invstd;
+  float *dgamma, *dbeta, *coef;
+  int blocks, C, accumulate;
+  float count;
+};
+__host__ __device__ __forceinline__ BnBwdFinArgs bn_bwd_fin_args_from_op(const HrOp& op) {
+  BnBwdFinArgs a;
+  a.partials = (const float*)op.p[HR_BN_BWD_FINALIZE_P_PARTIALS];
+  a.gamma = (const float*)op.p[HR_BN_BWD_FINALIZE_P_GAMMA];
+  a.save_mean = (const float*)op.p[HR_BN_BWD_FINALIZE_P_SAVE_MEAN];
+  a.save_invstd = (const float*)op.p[HR_BN_BWD_FINALIZE_P_SAVE_INVSTD];
+  a.dgamma = (float*)op.p[HR_BN_BWD_FINALIZE_P_DGAMMA]; a.dbeta = (float*)op.p[HR_BN_BWD_FINALIZE_P_DBETA];
+  a.coef = (float*)op.p[HR_BN_BWD_FINALIZE_P_COEF];
+  a.blocks = op.i[HR_BN_BWD_FINALIZE_I_BLOCKS]; a.C = op.i[HR_BN_BWD_FINALIZE_I_C];
+  a.accumulate = op.i[HR_BN_BWD_FINALIZE_I_ACCUMULATE]; a.count = op.f[HR_BN_BWD_FINALIZE_F_COUNT];
   return a;
 }
 
@@ -669,8 +705,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void grad_term_table_kernel(const HrOp* tab, int n) {
   int local;
   const HrOp& op = ew_table_find(tab, n, local);
-  const GradArgs a = ew_grad_args(op, false);
-  grad_term_block<T>(a, local, op.i[17]);
+  const GradArgs a = grad_args_from_op(op, false);
+  grad_term_block<T>(a, local, op.i[HR_EWJOB_I_BLOCKS]);
 }
 
 template <typename T>
@@ -680,7 +716,7 @@ __global__ __launch_bounds__(256) void pool_reduce_table_kernel(const HrOp* tab,
   const HrOp& op = ew_table_find(tab, n, local);
   PoolArgs a;
   pool_args_from_op(op, a);
-  pool_reduce_dispatch<T>(a, local, op.i[17], red);
+  pool_reduce_dispatch<T>(a, local, op.i[HR_EWJOB_I_BLOCKS], red);
 }
 
 // the forward sums of a HighResolutionModule's outputs (one per branch) as ONE launch: no fork / join around them
@@ -691,8 +727,9 @@ __global__ __launch_bounds__(256) void sum_terms_table_kernel(const HrOp* tab, i
   const HrOp& op = ew_table_find(tab, n, local);
   SumArgs a;
   sum_args_from_op(op, a);
-  a.eps = __builtin_bit_cast(float, op.i[18]);      // (a table job: i[16] / i[17] hold its block range, eps moved to i[18])
-  sum_terms_block<T, SUMS>(a, local, op.i[17], bn);
+  // (a table job: its block range lies over EPS_BITS)
+  a.eps = __builtin_bit_cast(float, op.i[HR_EWJOB_I_SUM_EPS_BITS]);
+  sum_terms_block<T, SUMS>(a, local, op.i[HR_EWJOB_I_BLOCKS], bn);
 }
 
 template <typename T>
@@ -700,16 +737,18 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_table_kernel(const HrOp* ta
   __shared__ float red[256 * 2 * TT<T>::VEC];
   int local;
   const HrOp& op = ew_table_find(tab, n, local);
-  const GradArgs a = ew_grad_args(op, true);
-  bn_bwd_reduce_block<T>(a, local, op.i[17], red);
+  const GradArgs a = grad_args_from_op(op, true);
+  bn_bwd_reduce_block<T>(a, local, op.i[HR_EWJOB_I_BLOCKS], red);
 }
 
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_table_kernel(const HrOp* tab, int n) {
   __shared__ double red[2][FIN_LANES][32];
   int local;
   const HrOp& op = ew_table_find(tab, n, local);
-  bn_bwd_finalize_block((const float*)op.p[0], op.i[0], op.i[1], op.f[0], (const float*)op.p[1], (const float*)op.p[2],
-                        (const float*)op.p[3], (float*)op.p[4], (float*)op.p[5], (float*)op.p[6], op.i[2], local, red);
+  const BnBwdFinArgs a = bn_bwd_fin_args_from_op(op);
+  bn_bwd_finalize_block(a.partials, a.blocks, a.C, a.count, a.gamma, a.save_mean, a.save_invstd, a.dgamma, a.dbeta,
+                        a.coef,
+                        a.accumulate, local, red);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1309,21 +1348,29 @@ extern "C" int hrnet_lincomb_f32(float* out, long long n, int k, const float* co
 // launchers
 // =========================================================================================
 int hr_launch_bn_finalize(const HrOp& op, hipStream_t s) {
-  const int tiles = op.i[0], C = op.i[1], training = op.i[2];
+  const int tiles = op.i[HR_BN_FINALIZE_I_TILES], C = op.i[HR_BN_FINALIZE_I_C],
+            training = op.i[HR_BN_FINALIZE_I_TRAINING];
   HR_REQUIRE(C > 0, "bn_finalize: C=%d", C);
-  HR_REQUIRE(op.p[1] && op.p[2] && op.p[6] && op.p[7], "bn_finalize: null pointer");
-  HR_REQUIRE(training ? (op.p[0] != nullptr && tiles > 0) : (op.p[3] && op.p[4]),
+  HR_REQUIRE(op.p[HR_BN_FINALIZE_P_GAMMA] && op.p[HR_BN_FINALIZE_P_BETA] && op.p[HR_BN_FINALIZE_P_SCALE] &&
+             op.p[HR_BN_FINALIZE_P_SHIFT], "bn_finalize: null pointer");
+  HR_REQUIRE(training ? (op.p[HR_BN_FINALIZE_P_STATS] != nullptr && tiles > 0) :
+             (op.p[HR_BN_FINALIZE_P_RUNNING_MEAN] && op.p[HR_BN_FINALIZE_P_RUNNING_VAR]),
              "bn_finalize: missing statistics");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, (const float*)op.p[0],
-                     tiles, C, op.f[0], (const float*)op.p[1], (const float*)op.p[2], (float*)op.p[3],
-                     (float*)op.p[4], (long long*)op.p[5], op.f[1], op.f[2], training, (float*)op.p[6],
-                     (float*)op.p[7], (float*)op.p[8], (float*)op.p[9]);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, s,
+                     (const float*)op.p[HR_BN_FINALIZE_P_STATS],
+                     tiles, C, op.f[HR_BN_FINALIZE_F_COUNT], (const float*)op.p[HR_BN_FINALIZE_P_GAMMA],
+                         (const float*)op.p[HR_BN_FINALIZE_P_BETA], (float*)op.p[HR_BN_FINALIZE_P_RUNNING_MEAN],
+                     (float*)op.p[HR_BN_FINALIZE_P_RUNNING_VAR],
+                         (long long*)op.p[HR_BN_FINALIZE_P_NUM_BATCHES_TRACKED], op.f[HR_BN_FINALIZE_F_MOMENTUM],
+                             op.f[HR_BN_FINALIZE_F_EPS], training, (float*)op.p[HR_BN_FINALIZE_P_SCALE],
+                     (float*)op.p[HR_BN_FINALIZE_P_SHIFT], (float*)op.p[HR_BN_FINALIZE_P_SAVE_MEAN],
+                         (float*)op.p[HR_BN_FINALIZE_P_SAVE_INVSTD]);
   return hr_check_launch("bn_finalize");
 }
 
 int hr_launch_sum_terms(const HrOp& op, hipStream_t s) {
   SumArgs a;
-  const int dtype = op.i[0];
+  const int dtype = op.i[HR_SUM_I_DTYPE];
   sum_args_from_op(op, a);
   HR_REQUIRE(a.nterms >= 1 && a.nterms <= 4, "sum_terms: nterms=%d", a.nterms);
   HR_REQUIRE(a.C % (dtype == HR_F32 ? 4 : 8) == 0, "sum_terms: C=%d", a.C);
@@ -1347,41 +1394,31 @@ int hr_launch_sum_terms(const HrOp& op, hipStream_t s) {
 }
 
 static int fill_grad_args(const HrOp& op, GradArgs& a, bool reduce) {
-  a.N = op.i[1]; a.H = op.i[2]; a.W = op.i[3]; a.C = op.i[4]; a.sh = op.i[5]; a.inner_relu = op.i[6];
-  a.accumulate = reduce ? 0 : op.i[7];
-  a.accumulate2 = reduce ? 0 : op.i[8];
-  a.dst2 = reduce ? nullptr : (char*)op.p[7];
-  if (reduce) {
-    a.partials = (float*)op.p[0]; a.dst = (char*)op.p[6]; a.coef = nullptr;
-  } else {
-    a.dst = (char*)op.p[0]; a.partials = nullptr; a.coef = (const float*)op.p[6];
-    HR_REQUIRE(!a.dst2 || (a.sh == 0 && !a.inner_relu), "grad_term: dst2 needs sh=0 and no inner ReLU");
-  }
-  a.g = (const char*)op.p[1]; a.mask = (const char*)op.p[2]; a.y = (const char*)op.p[3];
-  a.scale = (const float*)op.p[4]; a.shift = (const float*)op.p[5];
-  HR_REQUIRE(op.p[0] && a.g, "grad_term: null pointer");
+  a = grad_args_from_op(op, reduce);
+  HR_REQUIRE(reduce || !a.dst2 || (a.sh == 0 && !a.inner_relu), "grad_term: dst2 needs sh=0 and no inner ReLU");
+  HR_REQUIRE(op.p[HR_GRAD_TERM_P_DST] && a.g, "grad_term: null pointer");
   HR_REQUIRE(a.sh >= 0 && a.sh <= 4, "grad_term: shift %d", a.sh);
   HR_REQUIRE(!(a.inner_relu || a.coef || reduce) || a.y, "grad_term: y required");
-  HR_REQUIRE(a.C % (op.i[0] == HR_F32 ? 4 : 8) == 0, "grad_term: C=%d", a.C);
+  HR_REQUIRE(a.C % (op.i[HR_GRAD_TERM_I_DTYPE] == HR_F32 ? 4 : 8) == 0, "grad_term: C=%d", a.C);
   return 0;
 }
 
 int hr_launch_grad_term(const HrOp& op, hipStream_t s) {
   GradArgs a;
   if (int e = fill_grad_args(op, a, false)) return e;
-  const long long total = (long long)a.N * a.H * a.W * (a.C / (op.i[0] == HR_F32 ? 4 : 8));
-  const int cvs = a.C / (op.i[0] == HR_F32 ? 4 : 8);
+  const long long total = (long long)a.N * a.H * a.W * (a.C / (op.i[HR_GRAD_TERM_I_DTYPE] == HR_F32 ? 4 : 8));
+  const int cvs = a.C / (op.i[HR_GRAD_TERM_I_DTYPE] == HR_F32 ? 4 : 8);
   // large tensors (>= 4 grid-stride steps per thread): the variant that keeps the per-channel coefficients in registers
   if (a.sh == 0 && cvs <= 256 && total >= 4LL * 4096 * 256 && (long long)a.N * a.H * a.W < (1LL << 31)) {
     const int rows = 256 / cvs;
     const long long tot2 = ((long long)a.N * a.H * a.W + rows - 1) / rows * 256;
-    if (op.i[0] == HR_F32)
+    if (op.i[HR_GRAD_TERM_I_DTYPE] == HR_F32)
       hipLaunchKernelGGL(grad_term_rows_kernel<float>, dim3(ew_grid(tot2)), dim3(256), 0, s, a);
     else
       hipLaunchKernelGGL(grad_term_rows_kernel<bf16_t>, dim3(ew_grid(tot2)), dim3(256), 0, s, a);
     return hr_check_launch("grad_term");
   }
-  if (op.i[0] == HR_F32)
+  if (op.i[HR_GRAD_TERM_I_DTYPE] == HR_F32)
     hipLaunchKernelGGL(grad_term_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(grad_term_kernel<bf16_t>, dim3(ew_grid(total)), dim3(256), 0, s, a);
@@ -1413,18 +1450,17 @@ extern "C" int hrnet_reduce_blocks(int N, int H, int W, int C) {
 int hr_launch_bn_bwd_reduce(const HrOp& op, hipStream_t s) {
   GradArgs a;
   if (int e = fill_grad_args(op, a, true)) return e;
-  const int vec = op.i[0] == HR_F32 ? 4 : 8;
+  const int vec = op.i[HR_BN_BWD_REDUCE_I_DTYPE] == HR_F32 ? 4 : 8;
   HR_REQUIRE(a.C / vec <= 256, "bn_bwd_reduce: C=%d too wide", a.C);
   const int blocks = hrnet_reduce_blocks(a.N, a.H, a.W, a.C);
-  if (op.i[0] == HR_F32)
+  if (op.i[HR_BN_BWD_REDUCE_I_DTYPE] == HR_F32)
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(blocks), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, a);
   return hr_check_launch("bn_bwd_reduce");
 }
 
-// HR_OP_EW_TABLE: p[0] = device table of HrOp jobs, i[0] = jobs, i[1] = total blocks, i[2] = kind of the jobs
-// (HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE), i[3] = dtype
+// blocks of one job of a HR_OP_EW_TABLE launch (HR_EWJOB_I_BLOCKS)
 extern "C" int hrnet_ew_table_blocks(int kind, int dtype, int N, int H, int W, int C) {
   const int vec = dtype == HR_F32 ? 4 : 8;
   if (kind == HR_OP_GRAD_TERM) return (int)ew_grid((long long)N * H * W * (C / vec));
@@ -1436,10 +1472,11 @@ extern "C" int hrnet_ew_table_blocks(int kind, int dtype, int N, int H, int W, i
 }
 
 int hr_launch_ew_table(const HrOp& op, hipStream_t s) {
-  const int n = op.i[0], blocks = op.i[1], kind = op.i[2], dtype = op.i[3];
-  HR_REQUIRE(op.p[0] && n >= 1 && blocks >= 1, "ew_table: args");
+  const int n = op.i[HR_EW_TABLE_I_JOBS], blocks = op.i[HR_EW_TABLE_I_BLOCKS], kind = op.i[HR_EW_TABLE_I_KIND],
+            dtype = op.i[HR_EW_TABLE_I_DTYPE];
+  HR_REQUIRE(op.p[HR_EW_TABLE_P_TABLE] && n >= 1 && blocks >= 1, "ew_table: args");
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "ew_table: dtype %d", dtype);
-  const HrOp* tab = (const HrOp*)op.p[0];
+  const HrOp* tab = (const HrOp*)op.p[HR_EW_TABLE_P_TABLE];
   if (kind == HR_OP_GRAD_TERM) {
     if (dtype == HR_F32) hipLaunchKernelGGL(grad_term_table_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
     else hipLaunchKernelGGL(grad_term_table_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
@@ -1452,8 +1489,8 @@ int hr_launch_ew_table(const HrOp& op, hipStream_t s) {
     if (dtype == HR_F32) hipLaunchKernelGGL(pool_reduce_table_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
     else hipLaunchKernelGGL(pool_reduce_table_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
   } else if (kind == HR_OP_SUM_TERMS) {
-    // op.i[4] != 0: some job's BatchNorm comes as batch sums (the instantiation with the coefficient table)
-    const bool sums = op.i[4] != 0;
+    // SUMS != 0: some job's BatchNorm comes as batch sums (the instantiation with the coefficient table)
+    const bool sums = op.i[HR_EW_TABLE_I_SUMS] != 0;
     if (dtype == HR_F32) {
       if (sums) hipLaunchKernelGGL((sum_terms_table_kernel<float, true>), dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
       else hipLaunchKernelGGL((sum_terms_table_kernel<float, false>), dim3((unsigned)blocks), dim3(256), 0, s, tab, n);
@@ -1471,7 +1508,7 @@ int hr_launch_ew_table(const HrOp& op, hipStream_t s) {
 int hr_launch_pool_reduce(const HrOp& op, hipStream_t s) {
   PoolArgs a;
   pool_args_from_op(op, a);
-  const int dtype = op.i[0], vec = dtype == HR_F32 ? 4 : 8;
+  const int dtype = op.i[HR_POOL_I_DTYPE], vec = dtype == HR_F32 ? 4 : 8;
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "pool_reduce: dtype");
   HR_REQUIRE(a.g && a.nlev >= 1 && a.nlev <= 3 && a.N > 0 && a.C > 0 && a.C % vec == 0 && a.C / vec <= 256, "pool_reduce: args");
   HR_REQUIRE(a.H % (1 << a.nlev) == 0 && a.W % (1 << a.nlev) == 0, "pool_reduce: %dx%d is not a multiple of 2^%d", a.H, a.W, a.nlev);
@@ -1484,12 +1521,11 @@ int hr_launch_pool_reduce(const HrOp& op, hipStream_t s) {
 }
 
 int hr_launch_bn_bwd_finalize(const HrOp& op, hipStream_t s) {
-  const int blocks = op.i[0], C = op.i[1];
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[2] && op.p[3] && op.p[4] && op.p[5] && op.p[6],
+  const BnBwdFinArgs a = bn_bwd_fin_args_from_op(op);
+  HR_REQUIRE(a.partials && a.gamma && a.save_mean && a.save_invstd && a.dgamma && a.dbeta && a.coef,
              "bn_bwd_finalize: null pointer");
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, (const float*)op.p[0],
-                     blocks, C, op.f[0], (const float*)op.p[1], (const float*)op.p[2],
-                     (const float*)op.p[3], (float*)op.p[4], (float*)op.p[5], (float*)op.p[6], op.i[2]);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((a.C + 31) / 32), dim3(1024), 0, s, a.partials, a.blocks, a.C,
+                     a.count, a.gamma, a.save_mean, a.save_invstd, a.dgamma, a.dbeta, a.coef, a.accumulate);
   return hr_check_launch("bn_bwd_finalize");
 }
 
@@ -1584,15 +1620,15 @@ __global__ __launch_bounds__(256) void upsample_t_kernel(UpTArgs a) {
 }
 
 static int fill_cat_args(const HrOp& op, CatArgs& a, bool bwd) {
-  a.nbr = op.i[1]; a.N = op.i[2]; a.H = op.i[3]; a.W = op.i[4];
+  a.nbr = op.i[HR_CAT_I_NBR]; a.N = op.i[HR_CAT_I_N]; a.H = op.i[HR_CAT_I_H]; a.W = op.i[HR_CAT_I_W];
   HR_REQUIRE(a.nbr >= 1 && a.nbr <= 4, "bilinear_cat: nbr=%d", a.nbr);
-  a.cat = (char*)op.p[0];
+  a.cat = (char*)op.p[HR_CAT_P_CAT];
   HR_REQUIRE(a.cat, "bilinear_cat: null cat");
   int off = 0;
-  const int vec = op.i[0] == HR_F32 ? 4 : 8;
+  const int vec = op.i[HR_CAT_I_DTYPE] == HR_F32 ? 4 : 8;
   for (int k = 0; k < 4; ++k) {
-    a.hs[k] = op.i[5 + k]; a.ws[k] = op.i[9 + k]; a.cs[k] = op.i[13 + k];
-    a.xs[k] = (char*)op.p[1 + k];
+    a.hs[k] = op.i[HR_CAT_I_HS0 + k]; a.ws[k] = op.i[HR_CAT_I_WS0 + k]; a.cs[k] = op.i[HR_CAT_I_CS0 + k];
+    a.xs[k] = (char*)op.p[HR_CAT_P_X0 + k];
     a.coff[k] = off;
     if (k < a.nbr) {
       HR_REQUIRE(a.xs[k] && a.cs[k] % vec == 0 && a.hs[k] > 0 && a.ws[k] > 0, "bilinear_cat: branch %d", k);
@@ -1600,33 +1636,38 @@ static int fill_cat_args(const HrOp& op, CatArgs& a, bool bwd) {
     }
   }
   a.Ctot = off;
-  a.accumulate = bwd ? op.i[17] : 0;
-  a.align = op.f[0] != 0.f;   // (all integer slots are taken)
+  a.accumulate = bwd ? op.i[HR_CAT_I_ACCUMULATE] : 0;
+  a.align = op.f[HR_CAT_F_ALIGN] != 0.f;   // (all integer slots are taken)
   return 0;
 }
 
-// slots: i = {dtype, N, H, W, C, nout, align, h1, w1, h2, w2, h3, w3}, p = {G [N][H][W][C], out_k [N][h_k][w_k][C]}
+// slots HR_UPSAMPLE_T_*: G [N][H][W][C], out_k [N][h_k][w_k][C]
 int hr_upsample_t_tile(int dtype, const void* g, void* const* outs, const int* hs, const int* ws, int nout, int N, int H,
                        int W, int C, int align, hipStream_t s);
 
 int hr_launch_upsample_t(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], Cc = op.i[4], nout = op.i[5], align = op.i[6];
+  const int dtype = op.i[HR_UPSAMPLE_T_I_DTYPE], N = op.i[HR_UPSAMPLE_T_I_N], H = op.i[HR_UPSAMPLE_T_I_H],
+            W = op.i[HR_UPSAMPLE_T_I_W], Cc = op.i[HR_UPSAMPLE_T_I_C], nout = op.i[HR_UPSAMPLE_T_I_NOUT],
+            align = op.i[HR_UPSAMPLE_T_I_ALIGN];
   const int vec = dtype == HR_F32 ? 4 : 8;
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "upsample_t: dtype");
-  HR_REQUIRE(op.p[0] && N > 0 && H > 0 && W > 0 && Cc > 0 && Cc % vec == 0 && nout >= 1 && nout <= 3, "upsample_t: args");
+  HR_REQUIRE(op.p[HR_UPSAMPLE_T_P_G] && N > 0 && H > 0 && W > 0 && Cc > 0 && Cc % vec == 0 && nout >= 1 && nout <= 3,
+             "upsample_t: args");
   void* outs[3];
   int hs[3], ws[3];
   for (int k = 0; k < nout; ++k) {
-    outs[k] = op.p[1 + k]; hs[k] = op.i[7 + 2 * k]; ws[k] = op.i[8 + 2 * k];
+    outs[k] = op.p[HR_UPSAMPLE_T_P_OUT1 + k]; hs[k] = op.i[HR_UPSAMPLE_T_I_OUT_H1 + 2 * k];
+    ws[k] = op.i[HR_UPSAMPLE_T_I_OUT_W1 + 2 * k];
     HR_REQUIRE(outs[k] && hs[k] >= 1 && ws[k] >= 1 && hs[k] <= H && ws[k] <= W && ws[k] <= 256,
                "upsample_t: output %d: %dx%d from %dx%d", k, hs[k], ws[k], H, W);
   }
   // integer scales 2 / 4 / 8 (the head): all outputs from ONE pass over G (head_mix.hip)
-  if (op.i[13] == 0 && hr_upsample_t_tile(dtype, op.p[0], outs, hs, ws, nout, N, H, W, Cc, align, s) == 0)
+  if (op.i[HR_UPSAMPLE_T_I_STREAMED] == 0 && hr_upsample_t_tile(dtype, op.p[HR_UPSAMPLE_T_P_G], outs, hs, ws, nout, N,
+                                                                H, W, Cc, align, s) == 0)
     return hr_check_launch("upsample_t");
   for (int k = 0; k < nout; ++k) {
     UpTArgs a;
-    a.g = (const char*)op.p[0]; a.out = (char*)outs[k];
+    a.g = (const char*)op.p[HR_UPSAMPLE_T_P_G]; a.out = (char*)outs[k];
     a.N = N; a.H = H; a.W = W; a.C = Cc; a.hs = hs[k]; a.ws = ws[k]; a.align = align;
     HR_REQUIRE(2 * ((a.W + a.ws - 1) / a.ws) + 4 <= CATB_MAXW, "upsample_t: scale %d x %d too large", a.W, a.ws);
     const int cvtot = a.C / vec;
@@ -1651,8 +1692,8 @@ int hr_launch_upsample_t(const HrOp& op, hipStream_t s) {
 int hr_launch_bilinear_cat(const HrOp& op, hipStream_t s) {
   CatArgs a;
   if (int e = fill_cat_args(op, a, false)) return e;
-  const long long total = (long long)a.N * a.H * a.W * (a.Ctot / (op.i[0] == HR_F32 ? 4 : 8));
-  if (op.i[0] == HR_F32)
+  const long long total = (long long)a.N * a.H * a.W * (a.Ctot / (op.i[HR_CAT_I_DTYPE] == HR_F32 ? 4 : 8));
+  if (op.i[HR_CAT_I_DTYPE] == HR_F32)
     hipLaunchKernelGGL(bilinear_cat_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(bilinear_cat_kernel<bf16_t>, dim3(ew_grid(total)), dim3(256), 0, s, a);
@@ -1663,8 +1704,8 @@ int hr_launch_bilinear_cat_bwd(const HrOp& op, hipStream_t s) {
   CatArgs a;
   if (int e = fill_cat_args(op, a, true)) return e;
   for (int b = 0; b < a.nbr; ++b) {
-    const long long total = (long long)a.N * a.hs[b] * a.ws[b] * (a.cs[b] / (op.i[0] == HR_F32 ? 4 : 8));
-    if (op.i[0] == HR_F32)
+    const long long total = (long long)a.N * a.hs[b] * a.ws[b] * (a.cs[b] / (op.i[HR_CAT_I_DTYPE] == HR_F32 ? 4 : 8));
+    if (op.i[HR_CAT_I_DTYPE] == HR_F32)
       hipLaunchKernelGGL(bilinear_cat_bwd_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, s, a, b);
     else
       hipLaunchKernelGGL(bilinear_cat_bwd_kernel<bf16_t>, dim3(ew_grid(total)), dim3(256), 0, s, a, b);
@@ -1673,127 +1714,145 @@ int hr_launch_bilinear_cat_bwd(const HrOp& op, hipStream_t s) {
 }
 
 int hr_launch_im2col_stem(const HrOp& op, hipStream_t s) {
-  const int N = op.i[1], C = op.i[2], H = op.i[3], W = op.i[4], Ho = op.i[5], Wo = op.i[6], Kpad = op.i[7];
-  HR_REQUIRE(op.p[0] && op.p[1], "im2col_stem: null pointer");
+  const int N = op.i[HR_IM2COL_I_N], C = op.i[HR_IM2COL_I_C], H = op.i[HR_IM2COL_I_H], W = op.i[HR_IM2COL_I_W],
+            Ho = op.i[HR_IM2COL_I_HO], Wo = op.i[HR_IM2COL_I_WO], Kpad = op.i[HR_IM2COL_I_KPAD];
+  HR_REQUIRE(op.p[HR_IM2COL_P_IMG] && op.p[HR_IM2COL_P_COLS], "im2col_stem: null pointer");
   HR_REQUIRE(Kpad >= 9 * C && Ho == (H + 1) / 2 && Wo == (W + 1) / 2, "im2col_stem: shape");
   const long long total = (long long)N * Ho * Wo * Kpad;
   if (C == 3 && Kpad == 32) {
     const long long px = (long long)N * Ho * Wo;
-    if (op.i[0] == HR_F32)
-      hipLaunchKernelGGL(im2col_stem_pixel_kernel<float>, dim3(ew_grid(px)), dim3(256), 0, s, (const float*)op.p[0],
-                         (char*)op.p[1], N, H, W, Ho, Wo);
+    if (op.i[HR_IM2COL_I_DTYPE] == HR_F32)
+      hipLaunchKernelGGL(im2col_stem_pixel_kernel<float>, dim3(ew_grid(px)), dim3(256), 0, s,
+                         (const float*)op.p[HR_IM2COL_P_IMG],
+                         (char*)op.p[HR_IM2COL_P_COLS], N, H, W, Ho, Wo);
     else
-      hipLaunchKernelGGL(im2col_stem_pixel_kernel<bf16_t>, dim3(ew_grid(px)), dim3(256), 0, s, (const float*)op.p[0],
-                         (char*)op.p[1], N, H, W, Ho, Wo);
+      hipLaunchKernelGGL(im2col_stem_pixel_kernel<bf16_t>, dim3(ew_grid(px)), dim3(256), 0, s,
+                         (const float*)op.p[HR_IM2COL_P_IMG],
+                         (char*)op.p[HR_IM2COL_P_COLS], N, H, W, Ho, Wo);
     return hr_check_launch("im2col_stem");
   }
-  if (op.i[0] == HR_F32)
+  if (op.i[HR_IM2COL_I_DTYPE] == HR_F32)
     hipLaunchKernelGGL(im2col_stem_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, s,
-                       (const float*)op.p[0], (float*)op.p[1], N, C, H, W, Ho, Wo, Kpad);
+                       (const float*)op.p[HR_IM2COL_P_IMG], (float*)op.p[HR_IM2COL_P_COLS], N, C, H, W, Ho, Wo, Kpad);
   else
     hipLaunchKernelGGL(im2col_stem_kernel<bf16_t>, dim3(ew_grid(total)), dim3(256), 0, s,
-                       (const float*)op.p[0], (bf16_t*)op.p[1], N, C, H, W, Ho, Wo, Kpad);
+                       (const float*)op.p[HR_IM2COL_P_IMG], (bf16_t*)op.p[HR_IM2COL_P_COLS], N, C, H, W, Ho, Wo, Kpad);
   return hr_check_launch("im2col_stem");
 }
 
 int hr_launch_nhwc_to_nchw(const HrOp& op, hipStream_t s) {
-  const int N = op.i[1], HW = op.i[2] * op.i[3], Cp = op.i[4], C = op.i[5];
-  HR_REQUIRE(op.p[0] && op.p[1] && C <= Cp, "nhwc_to_nchw: args");
+  const int N = op.i[HR_LAYOUT_I_N], HW = op.i[HR_LAYOUT_I_H] * op.i[HR_LAYOUT_I_W], Cp = op.i[HR_LAYOUT_I_CP],
+            C = op.i[HR_LAYOUT_I_C];
+  HR_REQUIRE(op.p[HR_LAYOUT_P_SRC] && op.p[HR_LAYOUT_P_DST] && C <= Cp, "nhwc_to_nchw: args");
   dim3 grid((HW + 31) / 32, (C + 31) / 32, N);
-  if (op.i[0] == HR_F32)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)op.p[0],
-                       (float*)op.p[1], N, HW, Cp, C);
+  if (op.i[HR_LAYOUT_I_DTYPE] == HR_F32)
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)op.p[HR_LAYOUT_P_SRC],
+                       (float*)op.p[HR_LAYOUT_P_DST], N, HW, Cp, C);
   else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)op.p[0],
-                       (float*)op.p[1], N, HW, Cp, C);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)op.p[HR_LAYOUT_P_SRC],
+                       (float*)op.p[HR_LAYOUT_P_DST], N, HW, Cp, C);
   return hr_check_launch("nhwc_to_nchw");
 }
 
 int hr_launch_nchw_to_nhwc(const HrOp& op, hipStream_t s) {
-  const int N = op.i[1], HW = op.i[2] * op.i[3], Cp = op.i[4], C = op.i[5];
-  HR_REQUIRE(op.p[0] && op.p[1] && C <= Cp, "nchw_to_nhwc: args");
+  const int N = op.i[HR_LAYOUT_I_N], HW = op.i[HR_LAYOUT_I_H] * op.i[HR_LAYOUT_I_W], Cp = op.i[HR_LAYOUT_I_CP],
+            C = op.i[HR_LAYOUT_I_C];
+  HR_REQUIRE(op.p[HR_LAYOUT_P_SRC] && op.p[HR_LAYOUT_P_DST] && C <= Cp, "nchw_to_nhwc: args");
   dim3 grid((HW + 31) / 32, (Cp + 31) / 32, N);
-  if (op.i[0] == HR_F32)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, (const float*)op.p[0],
-                       (float*)op.p[1], N, HW, Cp, C);
+  if (op.i[HR_LAYOUT_I_DTYPE] == HR_F32)
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, (const float*)op.p[HR_LAYOUT_P_SRC],
+                       (float*)op.p[HR_LAYOUT_P_DST], N, HW, Cp, C);
   else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, s, (const float*)op.p[0],
-                       (bf16_t*)op.p[1], N, HW, Cp, C);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, s, (const float*)op.p[HR_LAYOUT_P_SRC],
+                       (bf16_t*)op.p[HR_LAYOUT_P_DST], N, HW, Cp, C);
   return hr_check_launch("nchw_to_nhwc");
 }
 
 int hr_launch_pack_weights(const HrOp& op, hipStream_t s) {
-  const int Cout = op.i[1], Cin = op.i[2], ks = op.i[3], Cout_pad = op.i[4], Cin_pad = op.i[5], mode = op.i[6];
-  HR_REQUIRE(op.p[0] && op.p[1] && mode >= 0 && mode <= 2, "pack_weights: args");
+  const int Cout = op.i[HR_PACK_I_COUT], Cin = op.i[HR_PACK_I_CIN], ks = op.i[HR_PACK_I_KS],
+            Cout_pad = op.i[HR_PACK_I_COUT_PAD], Cin_pad = op.i[HR_PACK_I_CIN_PAD], mode = op.i[HR_PACK_I_MODE];
+  HR_REQUIRE(op.p[HR_PACK_P_SRC] && op.p[HR_PACK_P_PACKED] && mode >= 0 && mode <= 2, "pack_weights: args");
   HR_REQUIRE(Cout_pad >= Cout && (mode == 2 ? Cin_pad >= Cin * ks * ks : Cin_pad >= Cin), "pack_weights: pads");
   const long long total = mode == 2 ? (long long)Cout_pad * Cin_pad : (long long)Cout_pad * ks * ks * Cin_pad;
-  if (op.i[0] == HR_F32)
+  if (op.i[HR_PACK_I_DTYPE] == HR_F32)
     hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(ew_grid(total)), dim3(256), 0, s,
-                       (const float*)op.p[0], (float*)op.p[1], Cout, Cin, ks, Cout_pad, Cin_pad, mode);
+                       (const float*)op.p[HR_PACK_P_SRC], (float*)op.p[HR_PACK_P_PACKED], Cout, Cin, ks, Cout_pad,
+                           Cin_pad, mode);
   else
     hipLaunchKernelGGL(pack_weights_kernel<bf16_t>, dim3(ew_grid(total)), dim3(256), 0, s,
-                       (const float*)op.p[0], (bf16_t*)op.p[1], Cout, Cin, ks, Cout_pad, Cin_pad, mode);
+                       (const float*)op.p[HR_PACK_P_SRC], (bf16_t*)op.p[HR_PACK_P_PACKED], Cout, Cin, ks, Cout_pad,
+                           Cin_pad, mode);
   return hr_check_launch("pack_weights");
 }
 
 int hr_launch_pack_table(const HrOp& op, hipStream_t s) {
-  const int n = op.i[1], blocks = op.i[2];
-  HR_REQUIRE(op.p[0] && n >= 1 && blocks >= 1, "pack_weights_table: args");
-  if (op.i[0] == HR_F32)
-    hipLaunchKernelGGL(pack_table_kernel<float>, dim3(blocks), dim3(256), 0, s, (const HrPackEnt*)op.p[0], n);
+  const int n = op.i[HR_PACK_TABLE_I_N], blocks = op.i[HR_PACK_TABLE_I_BLOCKS];
+  HR_REQUIRE(op.p[HR_PACK_TABLE_P_TABLE] && n >= 1 && blocks >= 1, "pack_weights_table: args");
+  if (op.i[HR_PACK_TABLE_I_DTYPE] == HR_F32)
+    hipLaunchKernelGGL(pack_table_kernel<float>, dim3(blocks), dim3(256), 0, s,
+                       (const HrPackEnt*)op.p[HR_PACK_TABLE_P_TABLE], n);
   else
-    hipLaunchKernelGGL(pack_table_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, (const HrPackEnt*)op.p[0], n);
+    hipLaunchKernelGGL(pack_table_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s,
+                       (const HrPackEnt*)op.p[HR_PACK_TABLE_P_TABLE], n);
   return hr_check_launch("pack_weights_table");
 }
 
 int hr_launch_bias_grad(const HrOp& op, hipStream_t s) {
-  const int pixels = op.i[1], Cp = op.i[2], C = op.i[3];
-  const int vec = op.i[0] == HR_F32 ? 4 : 8;
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[2] && C <= Cp && Cp % vec == 0 && Cp / vec <= 256, "bias_grad: args");
+  const int pixels = op.i[HR_BIAS_GRAD_I_PIXELS], Cp = op.i[HR_BIAS_GRAD_I_CP], C = op.i[HR_BIAS_GRAD_I_C];
+  const int vec = op.i[HR_BIAS_GRAD_I_DTYPE] == HR_F32 ? 4 : 8;
+  HR_REQUIRE(op.p[HR_BIAS_GRAD_P_DY] && op.p[HR_BIAS_GRAD_P_DBIAS] && op.p[HR_BIAS_GRAD_P_SCRATCH] && C <= Cp &&
+             Cp % vec == 0 && Cp / vec <= 256, "bias_grad: args");
   const int blocks = hrnet_reduce_blocks(1, 1, pixels, Cp);
-  if (op.i[0] == HR_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3(blocks), dim3(256), 0, s, (const char*)op.p[0],
-                       (float*)op.p[2], (long long)pixels, Cp);
+  if (op.i[HR_BIAS_GRAD_I_DTYPE] == HR_F32)
+    hipLaunchKernelGGL(colsum_kernel<float>, dim3(blocks), dim3(256), 0, s, (const char*)op.p[HR_BIAS_GRAD_P_DY],
+                       (float*)op.p[HR_BIAS_GRAD_P_SCRATCH], (long long)pixels, Cp);
   else
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, (const char*)op.p[0],
-                       (float*)op.p[2], (long long)pixels, Cp);
-  hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, (const float*)op.p[2],
-                     (float*)op.p[1], blocks, Cp, C, op.i[4]);
+    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, (const char*)op.p[HR_BIAS_GRAD_P_DY],
+                       (float*)op.p[HR_BIAS_GRAD_P_SCRATCH], (long long)pixels, Cp);
+  hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s,
+                     (const float*)op.p[HR_BIAS_GRAD_P_SCRATCH],
+                     (float*)op.p[HR_BIAS_GRAD_P_DBIAS], blocks, Cp, C, op.i[HR_BIAS_GRAD_I_ACCUMULATE]);
   return hr_check_launch("bias_grad");
 }
 
 int hr_launch_wgrad_reduce(const HrOp& op, hipStream_t s) {
-  const int nsplit = op.i[0], Cout = op.i[1], Cin = op.i[2], ks = op.i[3], Cout_real = op.i[4],
-            Cin_real = op.i[5], kflat = op.i[6];
-  HR_REQUIRE(op.p[0] && op.p[1] && nsplit >= 1, "wgrad_reduce: args");
+  const int nsplit = op.i[HR_WGRAD_REDUCE_I_NSPLIT], Cout = op.i[HR_WGRAD_REDUCE_I_COUT_PAD],
+            Cin = op.i[HR_WGRAD_REDUCE_I_CIN_PAD], ks = op.i[HR_WGRAD_REDUCE_I_KS],
+            Cout_real = op.i[HR_WGRAD_REDUCE_I_COUT], Cin_real = op.i[HR_WGRAD_REDUCE_I_CIN],
+            kflat = op.i[HR_WGRAD_REDUCE_I_KFLAT];
+  HR_REQUIRE(op.p[HR_WGRAD_REDUCE_P_SLABS] && op.p[HR_WGRAD_REDUCE_P_GRAD] && nsplit >= 1, "wgrad_reduce: args");
   HR_REQUIRE(Cout_real <= Cout && (kflat ? Cin_real * ks * ks <= Cin : Cin_real <= Cin), "wgrad_reduce: extents");
   const long long total = (long long)Cout_real * Cin_real * ks * ks;
   long long rgrid = (total + 63) / 64;
   if (rgrid > 4096) rgrid = 4096;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rgrid), dim3(256), 0, s, (const float*)op.p[0],
-                     (float*)op.p[1], nsplit, Cout, Cin, ks, Cout_real, Cin_real, kflat, op.i[7], op.i[8]);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rgrid), dim3(256), 0, s,
+                     (const float*)op.p[HR_WGRAD_REDUCE_P_SLABS],
+                     (float*)op.p[HR_WGRAD_REDUCE_P_GRAD], nsplit, Cout, Cin, ks, Cout_real, Cin_real, kflat,
+                         op.i[HR_WGRAD_REDUCE_I_ACCUMULATE], op.i[HR_WGRAD_REDUCE_I_LD]);
   return hr_check_launch("wgrad_reduce");
 }
 
 int hr_launch_wgrad_reduce_table(const HrOp& op, hipStream_t s) {
-  const int n = op.i[0], blocks = op.i[1];
-  HR_REQUIRE(op.p[0] && n >= 1 && blocks >= 1, "wgrad_reduce_table: args");
-  hipLaunchKernelGGL(wgrad_reduce_table_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const HrWredEnt*)op.p[0], n);
+  const int n = op.i[HR_TABLE_I_N], blocks = op.i[HR_TABLE_I_BLOCKS];
+  HR_REQUIRE(op.p[HR_TABLE_P_TABLE] && n >= 1 && blocks >= 1, "wgrad_reduce_table: args");
+  hipLaunchKernelGGL(wgrad_reduce_table_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                     (const HrWredEnt*)op.p[HR_TABLE_P_TABLE], n);
   return hr_check_launch("wgrad_reduce_table");
 }
 
 int hr_launch_bn_finalize_table(const HrOp& op, hipStream_t s) {
-  const int n = op.i[0], blocks = op.i[1];
-  HR_REQUIRE(op.p[0] && n >= 1 && blocks >= 1, "bn_finalize_table: args");
-  hipLaunchKernelGGL(bn_finalize_table_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const HrBnEnt*)op.p[0], n);
+  const int n = op.i[HR_TABLE_I_N], blocks = op.i[HR_TABLE_I_BLOCKS];
+  HR_REQUIRE(op.p[HR_TABLE_P_TABLE] && n >= 1 && blocks >= 1, "bn_finalize_table: args");
+  hipLaunchKernelGGL(bn_finalize_table_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                     (const HrBnEnt*)op.p[HR_TABLE_P_TABLE], n);
   return hr_check_launch("bn_finalize_table");
 }
 
 int hr_launch_fill(const HrOp& op, hipStream_t s) {
-  const long long bytes = ((long long)(uint32_t)op.i[1] << 32) | (uint32_t)op.i[0];
-  HR_REQUIRE(op.p[0] && bytes >= 0 && ((uintptr_t)op.p[0] % 16) == 0, "fill_zero: args");
+  const long long bytes = ((long long)(uint32_t)op.i[HR_FILL_I_BYTES_HI] << 32) | (uint32_t)op.i[HR_FILL_I_BYTES_LO];
+  HR_REQUIRE(op.p[HR_FILL_P_DST] && bytes >= 0 && ((uintptr_t)op.p[HR_FILL_P_DST] % 16) == 0, "fill_zero: args");
   const long long n16 = bytes / 16;
-  hipLaunchKernelGGL(fill_zero_kernel, dim3(ew_grid(n16 > 0 ? n16 : 1)), dim3(256), 0, s, (V16*)op.p[0],
-                     n16, (char*)op.p[0] + n16 * 16, (int)(bytes % 16));
+  hipLaunchKernelGGL(fill_zero_kernel, dim3(ew_grid(n16 > 0 ? n16 : 1)), dim3(256), 0, s, (V16*)op.p[HR_FILL_P_DST],
+                     n16, (char*)op.p[HR_FILL_P_DST] + n16 * 16, (int)(bytes % 16));
   return hr_check_launch("fill_zero");
 }

@@ -654,19 +654,23 @@ static int head_launch(HeadMixArgs& a, int dtype, int mode, hipStream_t s) {
 }
 
 int hr_launch_head_mix(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], C0 = op.i[4], Cout = op.i[5], nup = op.i[6];
+  const int dtype = op.i[HR_HEAD_MIX_I_DTYPE], N = op.i[HR_HEAD_MIX_I_N], H = op.i[HR_HEAD_MIX_I_H],
+            W = op.i[HR_HEAD_MIX_I_W], C0 = op.i[HR_HEAD_MIX_I_C0], Cout = op.i[HR_HEAD_MIX_I_COUT],
+            nup = op.i[HR_HEAD_MIX_I_NUP];
   HR_REQUIRE(hrnet_head_mix_supported(dtype, C0, Cout),
              "head_mix: bf16 with C0 %% 16 == 0 (<= 128) or f32 with C0 %% 4 == 0 and Cout <= 512 (got dtype %d, %d, %d)",
              dtype, C0, Cout);
   HR_REQUIRE(N > 0 && H > 0 && W > 0 && nup >= 0 && nup <= 3, "head_mix: shape");
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[3], "head_mix: null pointer");
+  HR_REQUIRE(op.p[HR_HEAD_MIX_P_X0] && op.p[HR_HEAD_MIX_P_W0] && op.p[HR_HEAD_MIX_P_Y], "head_mix: null pointer");
   HeadMixArgs a = {};
-  a.x = (const char*)op.p[0]; a.w = (const char*)op.p[1]; a.bias = (const float*)op.p[2]; a.y = (char*)op.p[3];
-  if (op.i[14]) a.rows = (float*)op.p[4]; else a.sums = (float*)op.p[4];
-  a.N = N; a.H = H; a.W = W; a.K = C0; a.Cout = Cout; a.nup = nup; a.align = op.i[7];
+  a.x = (const char*)op.p[HR_HEAD_MIX_P_X0]; a.w = (const char*)op.p[HR_HEAD_MIX_P_W0];
+  a.bias = (const float*)op.p[HR_HEAD_MIX_P_BIAS]; a.y = (char*)op.p[HR_HEAD_MIX_P_Y];
+  if (op.i[HR_HEAD_MIX_I_ROWS_MODE]) a.rows = (float*)op.p[HR_HEAD_MIX_P_STATS];
+  else a.sums = (float*)op.p[HR_HEAD_MIX_P_STATS];
+  a.N = N; a.H = H; a.W = W; a.K = C0; a.Cout = Cout; a.nup = nup; a.align = op.i[HR_HEAD_MIX_I_ALIGN];
   for (int u = 0; u < nup; ++u) {
-    a.up[u] = (const char*)op.p[5 + u];
-    a.uh[u] = op.i[8 + 2 * u]; a.uw[u] = op.i[9 + 2 * u];
+    a.up[u] = (const char*)op.p[HR_HEAD_MIX_P_T1 + u];
+    a.uh[u] = op.i[HR_HEAD_MIX_I_UP_H1 + 2 * u]; a.uw[u] = op.i[HR_HEAD_MIX_I_UP_W1 + 2 * u];
     HR_REQUIRE(a.up[u] && a.uh[u] > 0 && a.uw[u] > 0 && a.uh[u] <= H && a.uw[u] <= W,
                "head_mix: low-resolution term %d (%dx%d)", u, a.uh[u], a.uw[u]);
   }
@@ -680,17 +684,23 @@ int hr_launch_head_mix(const HrOp& op, hipStream_t s) {
 // slots: i = {dtype, N, H, W, K, Cout, mode, inner_relu}, p = {dY [N][H][W][K], wT packed [Cout][K] (hrnet_pack_weights
 //        mode 1 of the 1x1 layer), y raw [N][H][W][Cout], out (rows f32 | G), bn scale, bn shift, coef [3][Cout]}
 int hr_launch_head_bwd(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], K = op.i[4], Cout = op.i[5], mode = op.i[6];
+  const int dtype = op.i[HR_HEAD_BWD_I_DTYPE], N = op.i[HR_HEAD_BWD_I_N], H = op.i[HR_HEAD_BWD_I_H],
+            W = op.i[HR_HEAD_BWD_I_W], K = op.i[HR_HEAD_BWD_I_K], Cout = op.i[HR_HEAD_BWD_I_COUT],
+            mode = op.i[HR_HEAD_BWD_I_MODE];
   HR_REQUIRE(hrnet_head_mix_supported(dtype, K, Cout), "head_bwd: dtype %d, K %d, Cout %d not served", dtype, K, Cout);
   HR_REQUIRE(N > 0 && H > 0 && W > 0 && (mode == 1 || mode == 2), "head_bwd: shape / mode");
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[2] && op.p[3], "head_bwd: null pointer");
-  HR_REQUIRE((op.p[4] == nullptr) == (op.p[5] == nullptr), "head_bwd: scale/shift must come together");
-  HR_REQUIRE(mode == 1 || op.p[6], "head_bwd: mode 2 needs the coefficients");
+  HR_REQUIRE(op.p[HR_HEAD_BWD_P_DY] && op.p[HR_HEAD_BWD_P_WT] && op.p[HR_HEAD_BWD_P_Y] && op.p[HR_HEAD_BWD_P_OUT],
+             "head_bwd: null pointer");
+  HR_REQUIRE((op.p[HR_HEAD_BWD_P_BN_SCALE] == nullptr) == (op.p[HR_HEAD_BWD_P_BN_SHIFT] == nullptr),
+             "head_bwd: scale/shift must come together");
+  HR_REQUIRE(mode == 1 || op.p[HR_HEAD_BWD_P_COEF], "head_bwd: mode 2 needs the coefficients");
   HeadMixArgs a = {};
-  a.x = (const char*)op.p[0]; a.w = (const char*)op.p[1]; a.yin = (const char*)op.p[2];
-  if (mode == 1) a.rows = (float*)op.p[3]; else a.y = (char*)op.p[3];
-  a.bn_scale = (const float*)op.p[4]; a.bn_shift = (const float*)op.p[5]; a.coef = (const float*)op.p[6];
-  a.inner_relu = op.i[7];
+  a.x = (const char*)op.p[HR_HEAD_BWD_P_DY]; a.w = (const char*)op.p[HR_HEAD_BWD_P_WT];
+  a.yin = (const char*)op.p[HR_HEAD_BWD_P_Y];
+  if (mode == 1) a.rows = (float*)op.p[HR_HEAD_BWD_P_OUT]; else a.y = (char*)op.p[HR_HEAD_BWD_P_OUT];
+  a.bn_scale = (const float*)op.p[HR_HEAD_BWD_P_BN_SCALE]; a.bn_shift = (const float*)op.p[HR_HEAD_BWD_P_BN_SHIFT];
+  a.coef = (const float*)op.p[HR_HEAD_BWD_P_COEF];
+  a.inner_relu = op.i[HR_HEAD_BWD_I_INNER_RELU];
   a.N = N; a.H = H; a.W = W; a.K = K; a.Cout = Cout;
   return head_launch(a, dtype, mode, s);
 }

@@ -490,25 +490,27 @@ extern "C" int hrnet_wgrad_tiles(int dtype, int N, int Ho, int Wo, int Cout, int
 }
 
 int hr_launch_wgrad(const HrOp& op, hipStream_t s) {
-  const int dtype = op.i[0], N = op.i[1], H = op.i[2], W = op.i[3], Cin = op.i[4], Ho = op.i[5],
-            Wo = op.i[6], Cout = op.i[7], ks = op.i[8], stride = op.i[9], nsplit = op.i[11];
+  const int dtype = op.i[HR_WGRAD_I_DTYPE], N = op.i[HR_WGRAD_I_N], H = op.i[HR_WGRAD_I_H], W = op.i[HR_WGRAD_I_W],
+            Cin = op.i[HR_WGRAD_I_CIN], Ho = op.i[HR_WGRAD_I_HO], Wo = op.i[HR_WGRAD_I_WO],
+            Cout = op.i[HR_WGRAD_I_COUT], ks = op.i[HR_WGRAD_I_KS], stride = op.i[HR_WGRAD_I_STRIDE],
+            nsplit = op.i[HR_WGRAD_I_NSPLIT];
   HR_REQUIRE(dtype == HR_F32 || dtype == HR_BF16, "wgrad: bad dtype %d", dtype);
   HR_REQUIRE(ks == 1 || ks == 3, "wgrad: kernel size %d", ks);
   HR_REQUIRE(stride == 1 || (stride == 2 && ks == 3), "wgrad: stride %d", stride);
   HR_REQUIRE(Cin % (dtype == HR_F32 ? 4 : 8) == 0 && Cout % (dtype == HR_F32 ? 4 : 8) == 0,
              "wgrad: channel counts must be 16-byte multiples (Cin=%d Cout=%d)", Cin, Cout);
   HR_REQUIRE(nsplit >= 1, "wgrad: nsplit=%d", nsplit);
-  HR_REQUIRE(op.p[0] && op.p[1] && op.p[4], "wgrad: null pointer");
+  HR_REQUIRE(op.p[HR_WGRAD_P_X] && op.p[HR_WGRAD_P_DY] && op.p[HR_WGRAD_P_SLABS], "wgrad: null pointer");
   const int pad = ks / 2;
   HR_REQUIRE((H + 2 * pad - ks) / stride + 1 == Ho && (W + 2 * pad - ks) / stride + 1 == Wo,
              "wgrad: shape mismatch");
   const WgCfg c = choose_wg(dtype, Ho, Wo, Cout, ks, stride, Cin);
   WgradArgs a;
-  a.x = (const char*)op.p[0];
-  a.dy = (const char*)op.p[1];
-  a.in_scale = (const float*)op.p[2];
-  a.in_shift = (const float*)op.p[3];
-  a.slabs = (float*)op.p[4];
+  a.x = (const char*)op.p[HR_WGRAD_P_X];
+  a.dy = (const char*)op.p[HR_WGRAD_P_DY];
+  a.in_scale = (const float*)op.p[HR_WGRAD_P_IN_SCALE];
+  a.in_shift = (const float*)op.p[HR_WGRAD_P_IN_SHIFT];
+  a.slabs = (float*)op.p[HR_WGRAD_P_SLABS];
   a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout;
   const double es_ = dtype == HR_F32 ? 4.0 : 2.0;
   HR_REQUIRE((double)N * H * W * Cin * es_ < 2147483648.0 && (double)N * Ho * Wo * Cout * es_ < 2147483648.0,
@@ -518,11 +520,11 @@ int hr_launch_wgrad(const HrOp& op, hipStream_t s) {
   a.tiles_y = (Ho + c.th - 1) / c.th;
   a.tiles_x = (Wo + c.tw - 1) / c.tw;
   a.total_tiles = N * a.tiles_y * a.tiles_x;
-  a.in_relu = op.i[10];
-  a.atomic = op.i[12]; a.Cout_real = op.i[13]; a.Cin_real = op.i[14];
-  a.ld = op.i[15] ? op.i[15] : a.Cin_real;
-  HR_REQUIRE(!op.i[15] || (a.atomic && ks == 1 && op.i[15] >= a.Cin_real),
-             "wgrad: a row pitch (%d) belongs to an atomic 1x1 launch", op.i[15]);
+  a.in_relu = op.i[HR_WGRAD_I_IN_RELU];
+  a.atomic = op.i[HR_WGRAD_I_ATOMIC]; a.Cout_real = op.i[HR_WGRAD_I_COUT_REAL]; a.Cin_real = op.i[HR_WGRAD_I_CIN_REAL];
+  a.ld = op.i[HR_WGRAD_I_LD] ? op.i[HR_WGRAD_I_LD] : a.Cin_real;
+  HR_REQUIRE(!op.i[HR_WGRAD_I_LD] || (a.atomic && ks == 1 && op.i[HR_WGRAD_I_LD] >= a.Cin_real),
+             "wgrad: a row pitch (%d) belongs to an atomic 1x1 launch", op.i[HR_WGRAD_I_LD]);
   HR_REQUIRE(!a.atomic || (a.Cout_real >= 1 && a.Cout_real <= Cout && a.Cin_real >= 1 && a.Cin_real <= Cin),
              "wgrad: the atomic form needs the gradient's real channel counts (%d, %d)", a.Cout_real, a.Cin_real);
   dim3 grid((unsigned)nsplit, (unsigned)((Cout + c.bco - 1) / c.bco), (unsigned)((Cin + c.kc - 1) / c.kc));
@@ -536,10 +538,13 @@ extern "C" int hrnet_conv2d_wgrad(int dtype, const void* x, const void* dy, cons
                                   int nsplit, hr_stream_t stream) {
   HrOp op = {};
   op.kind = HR_OP_WGRAD;
-  const int iv[12] = {dtype, N, H, W, Cin, Ho, Wo, Cout, ks, stride, in_relu, nsplit};
-  for (int k = 0; k < 12; ++k) op.i[k] = iv[k];
-  op.p[0] = (void*)x; op.p[1] = (void*)dy; op.p[2] = (void*)in_scale; op.p[3] = (void*)in_shift;
-  op.p[4] = slabs;
+  op.i[HR_WGRAD_I_DTYPE] = dtype; op.i[HR_WGRAD_I_N] = N; op.i[HR_WGRAD_I_H] = H; op.i[HR_WGRAD_I_W] = W;
+  op.i[HR_WGRAD_I_CIN] = Cin; op.i[HR_WGRAD_I_HO] = Ho; op.i[HR_WGRAD_I_WO] = Wo; op.i[HR_WGRAD_I_COUT] = Cout;
+  op.i[HR_WGRAD_I_KS] = ks; op.i[HR_WGRAD_I_STRIDE] = stride; op.i[HR_WGRAD_I_IN_RELU] = in_relu;
+  op.i[HR_WGRAD_I_NSPLIT] = nsplit;
+  op.p[HR_WGRAD_P_X] = (void*)x; op.p[HR_WGRAD_P_DY] = (void*)dy; op.p[HR_WGRAD_P_IN_SCALE] = (void*)in_scale;
+  op.p[HR_WGRAD_P_IN_SHIFT] = (void*)in_shift;
+  op.p[HR_WGRAD_P_SLABS] = slabs;
   return hr_launch_wgrad(op, (hipStream_t)stream);
 }
 

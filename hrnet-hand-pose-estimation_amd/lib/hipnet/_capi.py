@@ -12,26 +12,19 @@ LIB_PATH = os.environ.get('HRNET_HIP_LIB', os.path.join(_PKG, 'csrc', 'libhrnet_
 
 HR_F32, HR_BF16 = 0, 1
 
+# op kinds of a recorded program (HR_OP_* of the header); lib/hipnet/ops.py names the slots of each
 (OP_CONV, OP_WGRAD, OP_WGRAD_REDUCE, OP_BN_FINALIZE, OP_SUM_TERMS, OP_GRAD_TERM, OP_BN_BWD_REDUCE,
  OP_BN_BWD_FINALIZE, OP_BILINEAR_CAT, OP_BILINEAR_CAT_BWD, OP_IM2COL_STEM, OP_NHWC_TO_NCHW,
- OP_NCHW_TO_NHWC, OP_PACK_WEIGHTS, OP_BIAS_GRAD, OP_FILL) = range(1, 17)
+ OP_NCHW_TO_NHWC, OP_PACK_WEIGHTS, OP_BIAS_GRAD, OP_FILL, OP_PACK_TABLE, OP_EVENT_RECORD, OP_STREAM_WAIT,
+ OP_WGRAD_REDUCE_TABLE, OP_BWD_FUSED, OP_BN_FINALIZE_TABLE, OP_BWD_PW, OP_CONV_SUM, OP_EW_TABLE, OP_HEAD_MIX,
+ OP_UPSAMPLE_T, OP_HEAD_BWD, OP_POOL_REDUCE) = range(1, 30)
+LANE_SLOT = 18
+ABI_VERSION = 2      # hrnet_abi_version() of the library this file binds (HrOp slot meanings, table structs)
 
 
 class HrOp(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('i', ctypes.c_int32 * 19), ('f', ctypes.c_float * 4),
                 ('p', ctypes.c_void_p * 14)]
-
-
-OP_PACK_TABLE, OP_EVENT_RECORD, OP_STREAM_WAIT, OP_WGRAD_REDUCE_TABLE, OP_BWD_FUSED, OP_BN_FINALIZE_TABLE = 17, 18, 19, 20, 21, 22
-OP_BWD_PW = 23
-OP_CONV_SUM = 24
-OP_EW_TABLE = 25
-OP_HEAD_MIX = 26
-OP_UPSAMPLE_T = 27
-OP_HEAD_BWD = 28
-OP_POOL_REDUCE = 29
-LANE_SLOT = 18
-ABI_VERSION = 2      # hrnet_abi_version() of the library this file binds (HrOp slot meanings, table structs)
 
 
 class HrPackEnt(ctypes.Structure):

@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _capi as C
+from . import ops
 
 
 def _dt(t):
@@ -227,12 +228,9 @@ class DilatedConv(torch.autograd.Function):
         g1 = torch.empty((co, ci, 1, 1), dtype=torch.float32, device=x.device)
         for t in range(9):
             # xs[p] = x[p + shift_t] (zero outside): one 1x1 identity conv over the displaced window
-            op = C.HrOp()
-            op.kind = C.OP_CONV
-            for k, v in enumerate((dt, N, H, W, cin, H, W, cin, 1, 1, 0, 0, 0)):
-                op.i[k] = v
-            op.i[15], op.i[16] = (t // 3 - 1) * d, (t % 3 - 1) * d
-            op.p[0], op.p[1], op.p[5] = x.data_ptr(), ident.data_ptr(), xs.data_ptr()
+            op = ops.make(C.OP_CONV, dtype=dt, n=N, h=H, w=W, cin=cin, ho=H, wo=W, cout=cin, ks=1, stride=1,
+                          in_dy=(t // 3 - 1) * d, in_dx=(t % 3 - 1) * d, x=x.data_ptr(), wgt=ident.data_ptr(),
+                          y=xs.data_ptr())
             C.call('hrnet_program_run', ctypes.byref(op), 1, C.stream_ptr())
             C.call('hrnet_conv2d_wgrad', dt, xs.data_ptr(), gy.data_ptr(), None, None, slabs.data_ptr(), N, H, W, cin, H, W,
                    cop, 1, 1, 0, ns, C.stream_ptr())

@@ -37,6 +37,7 @@ import os
 import torch
 
 from . import _capi as C
+from . import ops
 
 
 def _round_up(x, m):
@@ -131,17 +132,10 @@ class Program(object):
         self.tags = {}          # op index -> layer name (measurement scripts only)
         self.before_add = None  # called before every op is appended (the plan flushes a held-back sum there)
 
-    def add(self, kind, ints=(), floats=(), ptrs=(), lane=None):
+    def add(self, op, lane=None):
+        """append a built op (ops.make) on `lane` (None: the current lane); returns its index"""
         if self.before_add is not None:
             self.before_add(self.lane if lane is None else lane)
-        op = C.HrOp()
-        op.kind = kind
-        for k, v in enumerate(ints):
-            op.i[k] = int(v)
-        for k, v in enumerate(floats):
-            op.f[k] = float(v)
-        for k, v in enumerate(ptrs):
-            op.p[k] = v
         op.i[C.LANE_SLOT] = self.lane if lane is None else lane
         self.ops.append(op)
         self._arr = None
@@ -156,8 +150,8 @@ class Program(object):
         if not ev:
             raise RuntimeError('hrnet_event_create failed')
         self.events.append(ev)
-        self.add(C.OP_EVENT_RECORD, ptrs=(ev,), lane=src)
-        self.add(C.OP_STREAM_WAIT, ptrs=(ev,), lane=dst)
+        self.add(ops.make(C.OP_EVENT_RECORD, event=ev), lane=src)
+        self.add(ops.make(C.OP_STREAM_WAIT, event=ev), lane=dst)
 
     def fork(self, lanes):
         for l in lanes:
@@ -312,35 +306,35 @@ class Plan(object):
             bt, it = ps['bn_term'], ps['id_term']
             sm = self.bn_sums
             mb = bt.bn.mod
-            i = self.fwd.add(C.OP_CONV_SUM,
-                             ints=(self.dtid, x.N, x.H, x.W, cin, crec.Cout_pad, ks, 1 if (want_stats and sm) else 0),
-                             floats=((1.0 / bt.bn.count, mb.eps) if sm else ()),
-                             ptrs=(C.ptr(bt.act.t), C.ptr(crec.wf),
-                                   None if sm else C.ptr(bt.bn.scale), None if sm else C.ptr(bt.bn.shift),
-                                   C.ptr(bt.bn.sums) if sm else None, C.ptr(mb.weight) if sm else None,
-                                   C.ptr(mb.bias) if sm else None,
-                                   C.ptr(y.t), C.ptr(bnrec.sums) if (want_stats and sm) else None,
-                                   C.ptr(it.act.t), C.ptr(x.t)))
+            bn_in = (dict(in_inv_count=1.0 / bt.bn.count, in_eps=mb.eps, in_sums=C.ptr(bt.bn.sums),
+                          in_gamma=C.ptr(mb.weight), in_beta=C.ptr(mb.bias)) if sm
+                     else dict(in_scale=C.ptr(bt.bn.scale), in_shift=C.ptr(bt.bn.shift)))
+            kind = C.OP_CONV_SUM
+            i = self.fwd.add(ops.make(kind, dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=cin, cout=crec.Cout_pad, ks=ks,
+                                      stats_atomic=1 if (want_stats and sm) else 0, x=C.ptr(bt.act.t),
+                                      wgt=C.ptr(crec.wf), y=C.ptr(y.t),
+                                      stats=C.ptr(bnrec.sums) if (want_stats and sm) else None,
+                                      x2=C.ptr(it.act.t), side=C.ptr(x.t), **bn_in))
             self.n_fused_sums += 1
-            stats_slot = 8
         else:
-            stats_slot = 6
-            i = self.fwd.add(C.OP_CONV,
-                             ints=(self.dtid, x.N, x.H, x.W, cin, Ho, Wo, crec.Cout_pad, ks, stride, 0,
-                                   1 if xin.relu else 0, 0, 1 if (want_stats and self.bn_sums) else 0),
-                             floats=((1.0 / xin.bn.count, m_in.eps) if sums_in else ()),
-                             ptrs=(C.ptr(x.t), C.ptr(crec.wf),
-                                   C.ptr(xin.bn.scale) if (xin.bn and not sums_in) else None,
-                                   C.ptr(xin.bn.shift) if (xin.bn and not sums_in) else None,
-                                   C.ptr(self.net.bias_pad[crec.prefix]) if bias is not None else None,
-                                   C.ptr(y.t), C.ptr(bnrec.sums) if (want_stats and self.bn_sums) else None,
-                                   None, None, None, None,
-                                   C.ptr(xin.bn.sums) if sums_in else None, C.ptr(m_in.weight) if sums_in else None,
-                                   C.ptr(m_in.bias) if sums_in else None))
+            bn_in = {}
+            if sums_in:
+                bn_in = dict(in_inv_count=1.0 / xin.bn.count, in_eps=m_in.eps, in_sums=C.ptr(xin.bn.sums),
+                             in_gamma=C.ptr(m_in.weight), in_beta=C.ptr(m_in.bias))
+            elif xin.bn:
+                bn_in = dict(in_scale=C.ptr(xin.bn.scale), in_shift=C.ptr(xin.bn.shift))
+            kind = C.OP_CONV
+            i = self.fwd.add(ops.make(kind, dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=cin, ho=Ho, wo=Wo,
+                                      cout=crec.Cout_pad, ks=ks, stride=stride, in_relu=1 if xin.relu else 0,
+                                      stats_atomic=1 if (want_stats and self.bn_sums) else 0, x=C.ptr(x.t),
+                                      wgt=C.ptr(crec.wf),
+                                      bias=C.ptr(self.net.bias_pad[crec.prefix]) if bias is not None else None,
+                                      y=C.ptr(y.t), stats=C.ptr(bnrec.sums) if (want_stats and self.bn_sums) else None,
+                                      **bn_in))
         self.fwd.tags[i] = crec.prefix
         if want_stats and not self.bn_sums:
             self.max_stats = max(self.max_stats, tiles * 2 * crec.Cout_pad)
-            self._scratch(self.fwd, i, stats_slot, 'stats')
+            self._scratch(self.fwd, i, ops.slot(kind, 'p', 'stats'), 'stats')
         x.nuse += 1
         if bnrec is not None:
             y.bn = bnrec
@@ -348,15 +342,20 @@ class Plan(object):
             if self.training and self.bn_sums:
                 self.bn_finalize_list.append(bnrec)      # one table-driven launch at the end of the pass
             elif self.training:
-                m = bnrec.mod
-                j = self.fwd.add(C.OP_BN_FINALIZE, ints=(tiles, bnrec.C, 1),
-                                 floats=(y.pixels, m.momentum if m.momentum is not None else 0.1, m.eps),
-                                 ptrs=(None, C.ptr(m.weight), C.ptr(m.bias), C.ptr(m.running_mean),
-                                       C.ptr(m.running_var), C.ptr(m.num_batches_tracked), C.ptr(bnrec.scale),
-                                       C.ptr(bnrec.shift), C.ptr(bnrec.mean), C.ptr(bnrec.invstd)))
-                self._scratch(self.fwd, j, 0, 'stats')
+                self._bn_finalize(bnrec, tiles, y.pixels)
         self._tape(('conv', xin, crec, stride, y, bnrec))
         return Val(y, bnrec, relu)
+
+    def _bn_finalize(self, bnrec, rows, count):
+        """OP_BN_FINALIZE of a BatchNorm in training mode from `rows` statistic rows in the lane's scratch"""
+        m = bnrec.mod
+        j = self.fwd.add(ops.make(C.OP_BN_FINALIZE, tiles=rows, c=bnrec.C, training=1, count=count,
+                                  momentum=m.momentum if m.momentum is not None else 0.1, eps=m.eps,
+                                  gamma=C.ptr(m.weight), beta=C.ptr(m.bias), running_mean=C.ptr(m.running_mean),
+                                  running_var=C.ptr(m.running_var), num_batches_tracked=C.ptr(m.num_batches_tracked),
+                                  scale=C.ptr(bnrec.scale), shift=C.ptr(bnrec.shift), save_mean=C.ptr(bnrec.mean),
+                                  save_invstd=C.ptr(bnrec.invstd)))
+        self._scratch(self.fwd, j, ops.slot(C.OP_BN_FINALIZE, 'p', 'stats'), 'stats')
 
     def sum(self, terms, shifts, relu_out, name, batch=None):
         """batch: a list - the op is appended to it as a job of a table-driven launch (HR_OP_EW_TABLE) instead of
@@ -364,48 +363,32 @@ class Plan(object):
         t0 = terms[0].act
         sh0 = shifts[0]
         out = self._act(name, t0.N, t0.H << sh0, t0.W << sh0, t0.C)
-        ints = [self.dtid, out.N, out.H, out.W, out.C, len(terms), 1 if relu_out else 0]
-        ints += list(shifts) + [0] * (4 - len(terms))
-        ints += [1 if t.relu else 0 for t in terms] + [0] * (4 - len(terms))
-        ptrs = [C.ptr(out.t)]
-        ptrs += [C.ptr(t.act.t) for t in terms] + [None] * (4 - len(terms))
         # relu(bn(y) + identity) that closes a block: held back - if the very next op of this lane is the stride-1
         # conv that reads it, that conv forms the sum itself (hrnet_conv2d_sum); any other op emits it first
         bn_terms = [t for t in terms if t.bn is not None]
         hold = (self.fuse_sums and len(terms) == 2 and list(shifts) == [0, 0] and relu_out and len(bn_terms) == 1
                 and not bn_terms[0].relu and all(t.bn is not None or not t.relu for t in terms)
                 and (not self.bn_sums or t0.C <= 768) and batch is None)
-        emit = self.fwd.add
-        if hold:
-            held = []
-            emit = lambda *a, **k: held.append((a, k))
-        elif batch is not None:
-            def emit(kind, ints=(), floats=(), ptrs=()):
-                op = C.HrOp()
-                op.kind = kind
-                for k, v in enumerate(ints):
-                    op.i[k] = int(v)
-                for k, v in enumerate(floats):
-                    op.f[k] = float(v)
-                for k, v in enumerate(ptrs):
-                    op.p[k] = v
-                batch.append(op)
         if self.bn_sums and any(t.bn for t in terms):
-            import struct
-            mode = sum(1 << k for k, t in enumerate(terms) if t.bn)
-            ints += [mode, struct.unpack('i', struct.pack('f', float(next(t.bn.mod.eps for t in terms if t.bn))))[0]]
-            ptrs += [C.ptr(t.bn.sums) if t.bn else None for t in terms] + [None] * (4 - len(terms))
-            ptrs += [C.ptr(t.bn.mod.weight) if t.bn else None for t in terms] + [None] * (4 - len(terms))
-            floats = [1.0 / t.bn.count if t.bn else 0.0 for t in terms] + [0.0] * (4 - len(terms))
-            emit(C.OP_SUM_TERMS, ints=ints, floats=floats, ptrs=ptrs)
+            bn = dict(sums_mode=sum(1 << k for k, t in enumerate(terms) if t.bn),
+                      eps_bits=ops.f32_bits(next(t.bn.mod.eps for t in terms if t.bn)),
+                      scale=[C.ptr(t.bn.sums) if t.bn else None for t in terms],
+                      shift=[C.ptr(t.bn.mod.weight) if t.bn else None for t in terms],
+                      inv_count=[1.0 / t.bn.count if t.bn else 0.0 for t in terms])
         else:
-            ptrs += [C.ptr(t.bn.scale) if t.bn else None for t in terms] + [None] * (4 - len(terms))
-            ptrs += [C.ptr(t.bn.shift) if t.bn else None for t in terms] + [None] * (4 - len(terms))
-            emit(C.OP_SUM_TERMS, ints=ints, ptrs=ptrs)
+            bn = dict(scale=[C.ptr(t.bn.scale) if t.bn else None for t in terms],
+                      shift=[C.ptr(t.bn.shift) if t.bn else None for t in terms])
+        op = ops.make(C.OP_SUM_TERMS, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, nterms=len(terms),
+                      relu_out=1 if relu_out else 0, sh=shifts, relu=[1 if t.relu else 0 for t in terms],
+                      out=C.ptr(out.t), src=[C.ptr(t.act.t) for t in terms], **bn)
         if hold:
             self._flush_pending_sum(self.fwd.lane)
-            self._pending_sum[self.fwd.lane] = dict(out=out, lane=self.fwd.lane, op=held[0], bn_term=bn_terms[0],
+            self._pending_sum[self.fwd.lane] = dict(out=out, lane=self.fwd.lane, op=op, bn_term=bn_terms[0],
                                                     id_term=next(t for t in terms if t.bn is None))
+        elif batch is not None:
+            batch.append(op)
+        else:
+            self.fwd.add(op)
         for t in terms:
             t.act.nuse += 1
         self._tape(('sum', list(terms), list(shifts), relu_out, out))
@@ -417,21 +400,15 @@ class Plan(object):
         for l in ([lane] if lane is not None else sorted(self._pending_sum)):
             ps = self._pending_sum.pop(l, None)
             if ps is not None:
-                a, k = ps['op']
-                keep = self.fwd.lane
-                self.fwd.lane = ps['lane']
-                self.fwd.add(*a, **k)
-                self.fwd.lane = keep
+                self.fwd.add(ps['op'], lane=ps['lane'])
 
     def bilinear_cat(self, vals, name, align=False):
         a0 = vals[0].act
         ctot = sum(v.act.C for v in vals)
         cat = self._act(name, a0.N, a0.H, a0.W, ctot)
-        hs = [v.act.H for v in vals] + [0] * (4 - len(vals))
-        ws = [v.act.W for v in vals] + [0] * (4 - len(vals))
-        cs = [v.act.C for v in vals] + [0] * (4 - len(vals))
-        self.fwd.add(C.OP_BILINEAR_CAT, ints=[self.dtid, len(vals), a0.N, a0.H, a0.W] + hs + ws + cs,
-                     floats=(1.0 if align else 0.0,), ptrs=[C.ptr(cat.t)] + [C.ptr(v.act.t) for v in vals])
+        self.fwd.add(ops.make(C.OP_BILINEAR_CAT, dtype=self.dtid, nbr=len(vals), n=a0.N, h=a0.H, w=a0.W,
+                              hs=[v.act.H for v in vals], ws=[v.act.W for v in vals], cs=[v.act.C for v in vals],
+                              align=1.0 if align else 0.0, cat=C.ptr(cat.t), x=[C.ptr(v.act.t) for v in vals]))
         for v in vals:
             assert v.bn is None and not v.relu
             v.act.nuse += 1
@@ -453,26 +430,24 @@ class Plan(object):
         for j in range(1, len(vals)):
             xa = vals[j].act
             t = self._act('{}.t{}'.format(crec.prefix, j), xa.N, xa.H, xa.W, crec.Cout_pad)
-            i = self.fwd.add(C.OP_CONV, ints=(self.dtid, xa.N, xa.H, xa.W, xa.C, xa.H, xa.W, crec.Cout_pad, 1, 1, 0,
-                                              0, 0, 0),
-                             ptrs=(C.ptr(xa.t), C.ptr(wfs[j]), None, None, None, C.ptr(t.t), None))
+            i = self.fwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=xa.N, h=xa.H, w=xa.W, cin=xa.C, ho=xa.H, wo=xa.W,
+                                      cout=crec.Cout_pad, ks=1, stride=1, x=C.ptr(xa.t), wgt=C.ptr(wfs[j]), y=C.ptr(t.t)))
             self.fwd.tags[i] = '{}.t{}'.format(crec.prefix, j)
             ts.append(t)
         want_stats = bnrec is not None and self.training
         rows_mode = 0 if self.bn_sums else 1
-        ints = [self.dtid, x0.N, x0.H, x0.W, x0.C, crec.Cout_pad, len(ts), 1 if align else 0] + [0] * 6 + [rows_mode]
-        for k, t in enumerate(ts):
-            ints[8 + 2 * k], ints[9 + 2 * k] = t.H, t.W
         bias = crec.mod.bias
-        i = self.fwd.add(C.OP_HEAD_MIX, ints=ints,
-                         ptrs=[C.ptr(x0.t), C.ptr(wfs[0]), C.ptr(net.bias_pad[crec.prefix]) if bias is not None else None,
-                               C.ptr(y.t), C.ptr(bnrec.sums) if (want_stats and self.bn_sums) else None]
-                         + [C.ptr(t.t) for t in ts])
+        i = self.fwd.add(ops.make(C.OP_HEAD_MIX, dtype=self.dtid, n=x0.N, h=x0.H, w=x0.W, c0=x0.C, cout=crec.Cout_pad,
+                                  nup=len(ts), align=1 if align else 0, up_h=[t.H for t in ts], up_w=[t.W for t in ts],
+                                  rows_mode=rows_mode, x0=C.ptr(x0.t), w0=C.ptr(wfs[0]),
+                                  bias=C.ptr(net.bias_pad[crec.prefix]) if bias is not None else None, y=C.ptr(y.t),
+                                  stats=C.ptr(bnrec.sums) if (want_stats and self.bn_sums) else None,
+                                  t=[C.ptr(t.t) for t in ts]))
         self.fwd.tags[i] = crec.prefix
         rows = C.call('hrnet_head_mix_rows', x0.N, x0.H, x0.W)
         if want_stats and not self.bn_sums:
             self.max_stats = max(self.max_stats, rows * 2 * crec.Cout_pad)
-            self._scratch(self.fwd, i, 4, 'stats')
+            self._scratch(self.fwd, i, ops.slot(C.OP_HEAD_MIX, 'p', 'stats'), 'stats')
         for v in vals:
             assert v.bn is None and not v.relu
             v.act.nuse += 1
@@ -482,13 +457,7 @@ class Plan(object):
             if self.training and self.bn_sums:
                 self.bn_finalize_list.append(bnrec)
             elif self.training:
-                m = bnrec.mod
-                j = self.fwd.add(C.OP_BN_FINALIZE, ints=(rows, bnrec.C, 1),
-                                 floats=(y.pixels, m.momentum if m.momentum is not None else 0.1, m.eps),
-                                 ptrs=(None, C.ptr(m.weight), C.ptr(m.bias), C.ptr(m.running_mean),
-                                       C.ptr(m.running_var), C.ptr(m.num_batches_tracked), C.ptr(bnrec.scale),
-                                       C.ptr(bnrec.shift), C.ptr(bnrec.mean), C.ptr(bnrec.invstd)))
-                self._scratch(self.fwd, j, 0, 'stats')
+                self._bn_finalize(bnrec, rows, y.pixels)
         self._tape(('headmix', list(vals), crec, y, bnrec, ts, offs, align))
         self.n_head_mix = 1
         self._head_y = y
@@ -530,7 +499,8 @@ class Plan(object):
                 b.sums = self.bn_arena[off:off + 16 * b.C]
                 off += 16 * b.C
             nbytes = total * 4
-            self.fwd.add(C.OP_FILL, ints=(nbytes & 0xffffffff, nbytes >> 32), ptrs=(C.ptr(self.bn_arena),))
+            self.fwd.add(ops.make(C.OP_FILL, bytes_lo=ops.u32_bits(nbytes & 0xffffffff), bytes_hi=nbytes >> 32,
+                                  dst=C.ptr(self.bn_arena)))
         cv, bn = net.convs, self.bns
         if not self.training:
             # eval mode: every BatchNorm's affine from its running statistics, ONE table launch (306 launches of
@@ -540,8 +510,8 @@ class Plan(object):
             self.bn_finalize_list = []
         Ho, Wo = (H + 1) // 2, (W + 1) // 2
         cols = self._act('stem.cols', N, Ho, Wo, 32, grad=False)
-        self.in_op = self.fwd.add(C.OP_IM2COL_STEM, ints=(self.dtid, N, 3, H, W, Ho, Wo, 32),
-                                  ptrs=(None, C.ptr(cols.t)))
+        self.in_op = self.fwd.add(ops.make(C.OP_IM2COL_STEM, dtype=self.dtid, n=N, c=3, h=H, w=W, ho=Ho, wo=Wo, kpad=32,
+                                           cols=C.ptr(cols.t)))
         v = self.conv(Val(cols), cv['conv1'], 1, bn['bn1'], relu=True)
         v = self.conv(v, cv['conv2'], 2, bn['bn2'], relu=True)
         for k in range(4):
@@ -600,11 +570,10 @@ class Plan(object):
         out = self.conv(h, cv['last_layer.3'], 1, None, relu=False)
         self.out_act, self.inter_act = out.act, inter.act
         self.nj = cv['last_layer.3'].Cout
-        self.out_op = self.fwd.add(C.OP_NHWC_TO_NCHW, ints=(self.dtid, N, out.act.H, out.act.W, out.act.C, self.nj),
-                                   ptrs=(C.ptr(out.act.t), None))
-        self.inter_op = self.fwd.add(C.OP_NHWC_TO_NCHW,
-                                     ints=(self.dtid, N, inter.act.H, inter.act.W, inter.act.C, inter.act.C),
-                                     ptrs=(C.ptr(inter.act.t), None))
+        self.out_op = self.fwd.add(ops.make(C.OP_NHWC_TO_NCHW, dtype=self.dtid, n=N, h=out.act.H, w=out.act.W,
+                                            cp=out.act.C, c=self.nj, src=C.ptr(out.act.t)))
+        self.inter_op = self.fwd.add(ops.make(C.OP_NHWC_TO_NCHW, dtype=self.dtid, n=N, h=inter.act.H, w=inter.act.W,
+                                              cp=inter.act.C, c=inter.act.C, src=C.ptr(inter.act.t)))
         if self.bn_sums and self.bn_finalize_list:
             self._add_bn_finalize_table()
         self._flush_pending_sum()
@@ -634,7 +603,7 @@ class Plan(object):
         table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
         self.keep.append(table)
         self.fwd.lane = 0
-        self.fwd.add(C.OP_BN_FINALIZE_TABLE, ints=(len(self.bn_finalize_list), block), ptrs=(C.ptr(table),))
+        self.fwd.add(ops.make(C.OP_BN_FINALIZE_TABLE, n=len(self.bn_finalize_list), blocks=block, table=C.ptr(table)))
 
     def _hr_module(self, xs, pre, num_blocks):
         """HighResolutionModule.forward, pose_hrnet.py:247-266."""
@@ -711,26 +680,36 @@ class Plan(object):
                 self.tape_lanes[-1] = i if i in side else 0      # (the lane the backward pass works this branch on)
         self.fwd.lane = 0
         if batch:
-            block, sums_mode = 0, 0
-            for op in batch:
-                nb_ = C.call('hrnet_ew_table_blocks', C.OP_SUM_TERMS, self.dtid, op.i[1], op.i[2], op.i[3], op.i[4])
-                # (slots of a table job: i[16] = first block, i[17] = blocks; the eps of HR_OP_SUM_TERMS moves to i[18])
-                op.i[18] = op.i[16]
-                op.i[16], op.i[17] = block, nb_
-                block += nb_
-                sums_mode |= op.i[15]
-            arr = (C.HrOp * len(batch))(*batch)
-            raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
-            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-            self.keep.append(table)
-            self.fwd.add(C.OP_EW_TABLE, ints=(len(batch), block, C.OP_SUM_TERMS, self.dtid, 1 if sums_mode else 0),
-                         ptrs=(C.ptr(table),))
+            sums = any(op.i[ops.slot(C.OP_SUM_TERMS, 'i', 'sums_mode')] for op in batch)
+            self._add_ew_table(self.fwd, C.OP_SUM_TERMS, batch, sums=1 if sums else 0)
             self.n_batched_fwd_sums += len(batch)
         if sum_lanes:
             if batch is None:
                 self.fwd.join(side)
             self._tape(('join', side, 'sums'))
         return outs
+
+    def _add_ew_table(self, prog, kind, jobs, **fields):
+        """`jobs` (ops of one kind) as ONE OP_EW_TABLE launch of `prog`: every job gets its block range, the jobs go to
+        the device as the launch's table"""
+        dims = ops.SLOTS[kind]['i']
+        block = 0
+        for op in jobs:
+            if kind == C.OP_BN_BWD_FINALIZE:
+                nb = C.call('hrnet_ew_table_blocks', kind, self.dtid, 1, 1, 1, op.i[dims['C']])
+            else:
+                # (a pooled reduction is sized by its first level, H / 2 x W / 2)
+                sh = 1 if kind == C.OP_POOL_REDUCE else 0
+                nb = C.call('hrnet_ew_table_blocks', kind, self.dtid, op.i[dims['N']], op.i[dims['H']] >> sh,
+                            op.i[dims['W']] >> sh, op.i[dims['C']])
+            ops.set_job_blocks(op, block, nb)
+            block += nb
+        arr = (C.HrOp * len(jobs))(*jobs)
+        raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
+        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
+        self.keep.append(table)
+        prog.add(ops.make(C.OP_EW_TABLE, jobs=len(jobs), blocks=block, kind=kind, dtype=self.dtid, table=C.ptr(table),
+                          **fields))
 
     # ---- backward recording ---------------------------------------------------------------
     def _bn_backward(self, y, g_src, mask, sh, inner_relu, extra=None, pooled=None):
@@ -740,73 +719,62 @@ class Plan(object):
         b = y.bn
         blocks = C.call('hrnet_reduce_blocks', y.N, y.H, y.W, y.C)
         self.max_bwd_part = max(self.max_bwd_part, blocks * 2 * y.C)
-        m = b.mod
         # a reduction pass (no sums gathered by a producer) pools and masks the upstream gradient: it keeps that dz in
         # y.g, and the apply pass reads it from there instead of pooling and masking the full-resolution tensors
         # again (an up-sampled fuse term of branch 0 re-read 2 x 16.8 MB per term). HRNET_KEEP_DZ=0: both passes pool.
         keep_dz = None
         if y.bwd_rows is None and g_src != C.ptr(y.g) and _knob('HRNET_KEEP_DZ', '1') != '0':
             keep_dz = C.ptr(y.g)
+        shape = dict(dtype=self.dtid, n=y.N, h=y.H, w=y.W, c=y.C)
+        reduce_ = dict(shape, sh=sh, inner_relu=1 if inner_relu else 0, g=g_src, mask=mask, y=C.ptr(y.t),
+                       scale=C.ptr(b.scale), shift=C.ptr(b.shift), dz=keep_dz)
         if pooled is not None:
             # the reduction ran as one level of a HR_OP_POOL_REDUCE job (its dz is in y.g, its partial rows in `pooled`)
             part, pblocks = pooled
             keep_dz = C.ptr(y.g)
-            self._emit(C.OP_BN_BWD_FINALIZE, ints=(pblocks, y.C, 1), floats=(y.pixels,),
-                       ptrs=(C.ptr(part), C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd),
-                             C.ptr(self.net.grad_of(m.weight)), C.ptr(self.net.grad_of(m.bias)), C.ptr(b.coef)))
-        if pooled is not None:
-            pass
+            self._emit(self._bn_bwd_finalize_op(y, pblocks, C.ptr(part)))
         elif y.bwd_rows is not None:
             # the dgrad conv that finished g_src already gathered (sum dz, sum dz*y) in its epilogue
             rows, blocks = y.bwd_rows
             assert sh == 0
-            self._emit(C.OP_BN_BWD_FINALIZE, ints=(blocks, y.C, 1), floats=(y.pixels,),
-                       ptrs=(C.ptr(rows), C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd),
-                             C.ptr(self.net.grad_of(m.weight)), C.ptr(self.net.grad_of(m.bias)), C.ptr(b.coef)))
+            self._emit(self._bn_bwd_finalize_op(y, blocks, C.ptr(rows)))
         elif self._batch is not None:
             part = self._f32(blocks * 2 * y.C)          # (a job of a batched launch: partial rows of its own)
-            self._emit(C.OP_BN_BWD_REDUCE, ints=(self.dtid, y.N, y.H, y.W, y.C, sh, 1 if inner_relu else 0),
-                       ptrs=(C.ptr(part), g_src, mask, C.ptr(y.t), C.ptr(b.scale), C.ptr(b.shift), keep_dz))
-            self._emit(C.OP_BN_BWD_FINALIZE, ints=(blocks, y.C, 1), floats=(y.pixels,),
-                       ptrs=(C.ptr(part), C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd),
-                             C.ptr(self.net.grad_of(m.weight)), C.ptr(self.net.grad_of(m.bias)), C.ptr(b.coef)))
+            self._emit(ops.make(C.OP_BN_BWD_REDUCE, partials=C.ptr(part), **reduce_))
+            self._emit(self._bn_bwd_finalize_op(y, blocks, C.ptr(part)))
         else:
-            i = self.bwd.add(C.OP_BN_BWD_REDUCE, ints=(self.dtid, y.N, y.H, y.W, y.C, sh, 1 if inner_relu else 0),
-                             ptrs=(None, g_src, mask, C.ptr(y.t), C.ptr(b.scale), C.ptr(b.shift), keep_dz))
-            self._scratch(self.bwd, i, 0, 'bwdpart')
-            j = self.bwd.add(C.OP_BN_BWD_FINALIZE, ints=(blocks, y.C, 1), floats=(y.pixels,),
-                             ptrs=(None, C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd),
-                                   C.ptr(self.net.grad_of(m.weight)), C.ptr(self.net.grad_of(m.bias)), C.ptr(b.coef)))
-            self._scratch(self.bwd, j, 0, 'bwdpart')
-        ints = [self.dtid, y.N, y.H, y.W, y.C, sh, 1 if inner_relu else 0, 0, 0]
-        ptrs = [C.ptr(y.g), g_src, mask, C.ptr(y.t), C.ptr(b.scale), C.ptr(b.shift), C.ptr(b.coef), None]
+            i = self.bwd.add(ops.make(C.OP_BN_BWD_REDUCE, **reduce_))
+            self._scratch(self.bwd, i, ops.slot(C.OP_BN_BWD_REDUCE, 'p', 'partials'), 'bwdpart')
+            j = self.bwd.add(self._bn_bwd_finalize_op(y, blocks, None))
+            self._scratch(self.bwd, j, ops.slot(C.OP_BN_BWD_FINALIZE, 'p', 'partials'), 'bwdpart')
+        term = dict(shape, dst=C.ptr(y.g), y=C.ptr(y.t), scale=C.ptr(b.scale), shift=C.ptr(b.shift), coef=C.ptr(b.coef))
         if keep_dz is not None:
-            ints[5], ints[6] = 0, 0                   # dz as the reduction stored it: pooled and masked already
-            ptrs[1], ptrs[2] = keep_dz, None
+            term.update(g=keep_dz)                    # dz as the reduction stored it: pooled and masked already
+        else:
+            term.update(sh=sh, inner_relu=1 if inner_relu else 0, g=g_src, mask=mask)
         if extra is not None:
             assert sh == 0 and not inner_relu
-            ints[8] = 1 if extra.ginit else 0
-            ptrs[7] = C.ptr(extra.g)
+            term.update(accumulate2=1 if extra.ginit else 0, dst2=C.ptr(extra.g))
             extra.ginit = True
-        self._emit(C.OP_GRAD_TERM, ints=ints, ptrs=ptrs)
+        self._emit(ops.make(C.OP_GRAD_TERM, **term))
         y.bn_done = True
         y.ginit = True
 
+    def _bn_bwd_finalize_op(self, y, blocks, partials):
+        """OP_BN_BWD_FINALIZE of y's BatchNorm: `blocks` partial rows -> its coefficients, dgamma / dbeta added to"""
+        b, m = y.bn, y.bn.mod
+        return ops.make(C.OP_BN_BWD_FINALIZE, blocks=blocks, c=y.C, accumulate=1, count=y.pixels, partials=partials,
+                        gamma=C.ptr(m.weight), save_mean=C.ptr(b.mean), save_invstd=C.ptr(b.invstd),
+                        dgamma=C.ptr(self.net.grad_of(m.weight)), dbeta=C.ptr(self.net.grad_of(m.bias)),
+                        coef=C.ptr(b.coef))
+
     # ---- batched element-wise jobs (the backward of a HighResolutionModule's fuse sums) ----
-    def _emit(self, kind, ints=(), floats=(), ptrs=()):
-        """an HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE op: its own launch, or - while a batch is
-        open - a job of the batched launch of its kind (HR_OP_EW_TABLE)"""
+    def _emit(self, op):
+        """an HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE / HR_OP_POOL_REDUCE op: its own launch, or -
+        while a batch is open - a job of the batched launch of its kind (HR_OP_EW_TABLE)"""
         if self._batch is None:
-            return self.bwd.add(kind, ints=ints, floats=floats, ptrs=ptrs)
-        op = C.HrOp()
-        op.kind = kind
-        for k, v in enumerate(ints):
-            op.i[k] = int(v)
-        for k, v in enumerate(floats):
-            op.f[k] = float(v)
-        for k, v in enumerate(ptrs):
-            op.p[k] = v
-        self._batch[kind].append(op)
+            return self.bwd.add(op)
+        self._batch[op.kind].append(op)
         return None
 
     def _flush_batch(self):
@@ -817,31 +785,16 @@ class Plan(object):
         self.bwd.lane = 0
         for kind in (C.OP_POOL_REDUCE, C.OP_BN_BWD_REDUCE, C.OP_BN_BWD_FINALIZE, C.OP_GRAD_TERM):
             jobs = batch[kind]
-            if not jobs:
-                continue
-            block = 0
-            for op in jobs:
-                if kind == C.OP_BN_BWD_FINALIZE:
-                    nb = C.call('hrnet_ew_table_blocks', kind, self.dtid, 1, 1, 1, op.i[1])
-                elif kind == C.OP_POOL_REDUCE:
-                    nb = C.call('hrnet_ew_table_blocks', kind, self.dtid, op.i[1], op.i[2] >> 1, op.i[3] >> 1, op.i[4])
-                else:
-                    nb = C.call('hrnet_ew_table_blocks', kind, self.dtid, op.i[1], op.i[2], op.i[3], op.i[4])
-                op.i[16], op.i[17] = block, nb
-                block += nb
-            arr = (C.HrOp * len(jobs))(*jobs)
-            raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
-            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-            self.keep.append(table)
-            self.bwd.add(C.OP_EW_TABLE, ints=(len(jobs), block, kind, self.dtid), ptrs=(C.ptr(table),))
-            self.n_batched_jobs += len(jobs)
+            if jobs:
+                self._add_ew_table(self.bwd, kind, jobs)
+                self.n_batched_jobs += len(jobs)
 
     def _build_backward(self):
         net = self.net
         # d(heatmaps) NCHW f32 -> NHWC grad of the final conv; d(inter_feat) likewise (optional)
         oa = self.out_act
-        self.gout_op = self.bwd.add(C.OP_NCHW_TO_NHWC, ints=(self.dtid, oa.N, oa.H, oa.W, oa.C, self.nj),
-                                    ptrs=(None, C.ptr(oa.g)))
+        self.gout_op = self.bwd.add(ops.make(C.OP_NCHW_TO_NHWC, dtype=self.dtid, n=oa.N, h=oa.H, w=oa.W, cp=oa.C,
+                                             c=self.nj, dst=C.ptr(oa.g)))
         oa.ginit = True
         # Weight gradients by float atomics (default): every workgroup of a weight-gradient / fused backward launch ADDS
         # its tile straight into the OIHW f32 gradient (3x3 tiles go through LDS so that a wave instruction covers 64
@@ -963,9 +916,7 @@ class Plan(object):
                     self.bwd.fork(e[1])
                 else:
                     self.bwd.join(e[1])
-                if e[0] == 'join':
-                    pass
-                else:
+                if e[0] == 'fork':
                     if self.defer_wgrad and ti == first_fork:
                         self._emit_deferred_wgrads()
                     if self.wlane:
@@ -980,14 +931,11 @@ class Plan(object):
                 _, vals, cat, align = e
                 if cat is self.inter_act and self.inter_gop is None:
                     self.inter_gop = len(self.bwd)     # optional external gradient of inter_feat joins here
-                hs = [v.act.H for v in vals] + [0] * (4 - len(vals))
-                ws = [v.act.W for v in vals] + [0] * (4 - len(vals))
-                cs = [v.act.C for v in vals] + [0] * (4 - len(vals))
                 assert not any(v.act.ginit for v in vals)
-                self.bwd.add(C.OP_BILINEAR_CAT_BWD,
-                             ints=[self.dtid, len(vals), cat.N, cat.H, cat.W] + hs + ws + cs + [0],
-                             floats=(1.0 if align else 0.0,),
-                             ptrs=[C.ptr(cat.g)] + [C.ptr(v.act.g) for v in vals])
+                self.bwd.add(ops.make(C.OP_BILINEAR_CAT_BWD, dtype=self.dtid, nbr=len(vals), n=cat.N, h=cat.H, w=cat.W,
+                                      hs=[v.act.H for v in vals], ws=[v.act.W for v in vals],
+                                      cs=[v.act.C for v in vals], align=1.0 if align else 0.0, cat=C.ptr(cat.g),
+                                      x=[C.ptr(v.act.g) for v in vals]))
                 for v in vals:
                     v.act.ginit = True
             elif e[0] == 'headmix':
@@ -1018,12 +966,12 @@ class Plan(object):
                         and _knob('HRNET_POOL_REDUCE', '1') != '0' and _knob('HRNET_KEEP_DZ', '1') != '0'):
                     L = len(ups)
                     pblocks = C.call('hrnet_ew_table_blocks', C.OP_POOL_REDUCE, self.dtid, out.N, out.H >> 1, out.W >> 1, out.C)
-                    ptrs = [C.ptr(out.g), mask]
                     for sh, t in ups:
-                        part = self._f32(pblocks * 2 * out.C)
-                        ptrs += [C.ptr(t.act.t), C.ptr(t.act.g), C.ptr(part)]
-                        pooled[id(t.act)] = (part, pblocks)
-                    self._emit(C.OP_POOL_REDUCE, ints=(self.dtid, out.N, out.H, out.W, out.C, L), ptrs=ptrs)
+                        pooled[id(t.act)] = (self._f32(pblocks * 2 * out.C), pblocks)
+                    self._emit(ops.make(C.OP_POOL_REDUCE, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, nlev=L,
+                                        g=C.ptr(out.g), mask=mask, y=[C.ptr(t.act.t) for _, t in ups],
+                                        dz=[C.ptr(t.act.g) for _, t in ups],
+                                        partials=[C.ptr(pooled[id(t.act)][0]) for _, t in ups]))
                 for t, sh in zip(terms, shifts):
                     a = t.act
                     if t is paired[1]:
@@ -1035,9 +983,8 @@ class Plan(object):
                     else:
                         # accumulate d(post-activation value); BN backward runs at the producer
                         assert sh == 0
-                        self._emit(C.OP_GRAD_TERM,
-                                   ints=(self.dtid, a.N, a.H, a.W, a.C, 0, 0, 1 if a.ginit else 0),
-                                   ptrs=(C.ptr(a.g), C.ptr(out.g), mask, None, None, None, None))
+                        self._emit(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=a.N, h=a.H, w=a.W, c=a.C,
+                                            accumulate=1 if a.ginit else 0, dst=C.ptr(a.g), g=C.ptr(out.g), mask=mask))
                         a.ginit = True
             elif e[0] == 'conv':
                 _, xin, crec, stride, y, bnrec = e
@@ -1055,9 +1002,9 @@ class Plan(object):
                 if crec.mod.bias is not None and not (bnrec is not None and self.training):
                     blocks = C.call('hrnet_reduce_blocks', 1, 1, y.pixels, y.C)
                     self.max_bwd_part = max(self.max_bwd_part, blocks * y.C)
-                    i = self.bwd.add(C.OP_BIAS_GRAD, ints=(self.dtid, y.pixels, y.C, crec.Cout, 1),
-                                     ptrs=(C.ptr(y.g), C.ptr(net.grad_of(crec.mod.bias)), None))
-                    self._scratch(self.bwd, i, 2, 'bwdpart')
+                    i = self.bwd.add(ops.make(C.OP_BIAS_GRAD, dtype=self.dtid, pixels=y.pixels, cp=y.C, c=crec.Cout,
+                                              accumulate=1, dy=C.ptr(y.g), dbias=C.ptr(net.grad_of(crec.mod.bias))))
+                    self._scratch(self.bwd, i, ops.slot(C.OP_BIAS_GRAD, 'p', 'scratch'), 'bwdpart')
                 # the weight gradient is off the critical path: it runs on its own lane once dY is final
                 if self.wlane and (self.wlane_all or lane == 0):
                     self.bwd.sync(lane, self.wlane)
@@ -1085,36 +1032,35 @@ class Plan(object):
                         nsplit -= 1
                 # (the stem's weights are a flattened 3x3x3 kernel over im2col columns: its slab layout stays)
                 direct = self.batch_wred and self.wgrad_atomic and not crec.stem
-                wints = (self.dtid, x.N, x.H, x.W, x.C, y.H, y.W, y.C, ks, stride, 1 if xin.relu else 0, nsplit,
-                         1 if direct else 0, crec.Cout, crec.Cin)
-                wptrs = [C.ptr(x.t), C.ptr(y.g), C.ptr(xin.bn.scale) if xin.bn else None,
-                         C.ptr(xin.bn.shift) if xin.bn else None, None]
+                wgrad = dict(dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, ho=y.H, wo=y.W, cout=y.C, ks=ks, stride=stride,
+                             in_relu=1 if xin.relu else 0, nsplit=nsplit, atomic=1 if direct else 0,
+                             cout_real=crec.Cout, cin_real=crec.Cin, x=C.ptr(x.t), dy=C.ptr(y.g),
+                             in_scale=C.ptr(xin.bn.scale) if xin.bn else None,
+                             in_shift=C.ptr(xin.bn.shift) if xin.bn else None)
                 if direct:
-                    wptrs[4] = C.ptr(net.grad_of(w))
+                    wop = ops.make(C.OP_WGRAD, slabs=C.ptr(net.grad_of(w)), **wgrad)
                     if deferred:
-                        self._deferred.append((wints, wptrs, None, 2.0 * x.N * y.H * y.W * y.C * x.C * ks * ks,
-                                               net.offsets[id(w)][0]))
+                        self._deferred.append((wop, None, wflops, net.offsets[id(w)][0]))
                     elif self.offload_wgrad and lane == 0 and not in_region:
                         l = 1 + self._offload_rr % max(1, self.nlanes - 1)
                         self._offload_rr += 1
                         self.bwd.sync(0, l)
-                        self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs, lane=l)
+                        self.bwd.add(wop, lane=l)
                         self._offload_lanes.add(l)
                     else:
-                        self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs)
+                        self.bwd.add(wop)
                         if lane == 0:
                             self._wred_bytes += crec.Cout * crec.Cin * crec.ks * crec.ks * 4
                 elif self.batch_wred:
                     slabs = self._f32(nsplit * y.C * ks * ks * x.C)
                     self.slab_bytes += slabs.numel() * 4
-                    wptrs[4] = C.ptr(slabs)
+                    wop = ops.make(C.OP_WGRAD, slabs=C.ptr(slabs), **wgrad)
                     ent = dict(slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w)), nsplit=nsplit, Cout_pad=y.C, Cin_pad=x.C,
                                ks=crec.ks if crec.stem else ks, Cout=crec.Cout, Cin=crec.Cin, kflat=1 if crec.stem else 0,
                                accumulate=1)
                     if deferred:
                         # x.t, y.g and the BatchNorm coefficients of xin stay untouched until the program ends
-                        self._deferred.append((wints, wptrs, ent, 2.0 * x.N * y.H * y.W * y.C * x.C * ks * ks,
-                                               net.offsets[id(w)][0]))
+                        self._deferred.append((wop, ent, wflops, net.offsets[id(w)][0]))
                     elif self.offload_wgrad and lane == 0 and not in_region:
                         # a single-lane part of the pass (head, transition1, stem): its weight gradients are off the
                         # dependency chain - they go to a side lane, which idles there (the head) or carries the
@@ -1122,24 +1068,23 @@ class Plan(object):
                         l = 1 + self._offload_rr % max(1, self.nlanes - 1)
                         self._offload_rr += 1
                         self.bwd.sync(0, l)
-                        self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs, lane=l)
+                        self.bwd.add(wop, lane=l)
                         self._wred.setdefault(l, []).append(ent)
                         self._offload_lanes.add(l)
                     else:
-                        self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs)
+                        self.bwd.add(wop)
                         self._wred.setdefault(self.bwd.lane, []).append(ent)
                         if lane == 0:
                             self._wred_bytes += crec.Cout * crec.Cin * crec.ks * crec.ks * 4
                 else:
                     self.max_slab = max(self.max_slab, nsplit * y.C * ks * ks * x.C)
-                    i = self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs)
-                    self._scratch(self.bwd, i, 4, 'slab')
-                    i = self.bwd.add(C.OP_WGRAD_REDUCE,
-                                     ints=(nsplit, y.C, x.C, ks, crec.Cout, crec.Cin, 1 if crec.stem else 0, 1),
-                                     ptrs=(None, C.ptr(net.grad_of(w))))
-                    self._scratch(self.bwd, i, 0, 'slab')
-                    if crec.stem:
-                        self.bwd.ops[i].i[3] = crec.ks   # real taps of the flattened stem kernel
+                    i = self.bwd.add(ops.make(C.OP_WGRAD, **wgrad))
+                    self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD, 'p', 'slabs'), 'slab')
+                    # (ks: the real taps of the flattened stem kernel)
+                    i = self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=nsplit, cout_pad=y.C, cin_pad=x.C,
+                                              ks=crec.ks if crec.stem else ks, cout=crec.Cout, cin=crec.Cin,
+                                              kflat=1 if crec.stem else 0, accumulate=1, grad=C.ptr(net.grad_of(w))))
+                    self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD_REDUCE, 'p', 'slabs'), 'slab')
                 self.bwd.lane = lane
                 if (x is self._head_y and x.g is not None and xin.bn is not None and self.training and ks == 1
                         and crec.mod.weight.shape[0] <= y.C and _knob('HRNET_HEAD_BWD', '1') != '0'
@@ -1149,25 +1094,25 @@ class Plan(object):
                     # the apply launch in _head_mix_backward (hrnet_head_bwd): dz is never stored or re-read
                     nrows = C.call('hrnet_head_mix_rows', x.N, x.H, x.W)
                     rows = self._f32(nrows * 2 * x.C)
-                    self.bwd.add(C.OP_HEAD_BWD, ints=(self.dtid, x.N, x.H, x.W, y.C, x.C, 1, 1 if xin.relu else 0),
-                                 ptrs=(C.ptr(y.g), C.ptr(crec.wd), C.ptr(x.t), C.ptr(rows), C.ptr(xin.bn.scale),
-                                       C.ptr(xin.bn.shift), None))
+                    self.bwd.add(ops.make(C.OP_HEAD_BWD, dtype=self.dtid, n=x.N, h=x.H, w=x.W, k=y.C, cout=x.C, mode=1,
+                                          inner_relu=1 if xin.relu else 0, dy=C.ptr(y.g), wt=C.ptr(crec.wd), y=C.ptr(x.t),
+                                          out=C.ptr(rows), bn_scale=C.ptr(xin.bn.scale), bn_shift=C.ptr(xin.bn.shift)))
                     x.bwd_rows = (rows, nrows)
                     x.ginit = True
                     self._head_bwd = (y, crec, 1 if xin.relu else 0)
                     self.n_fused_bwdstats += 1
                 elif x.g is not None:
                     # input gradient = conv of dY with the transposed kernel (zero-stuffed for stride 2)
-                    ptrs = [C.ptr(y.g), C.ptr(crec.wd), None, None, None, C.ptr(x.g), None, None, None, None, None]
+                    bs = {}     # backward statistics: the BS_* slots, the rows and the masked store
                     last = (first_use.get(id(x)) == ti and use_lanes.get(id(x)) == {lane}
                             and x is not self.inter_act)
                     target = None
                     if fuse_stats and last and xin.bn is not None and x.nuse == 1:
                         # x is a raw conv output read through its BatchNorm (+ReLU) by this conv alone
                         target = x
-                        ptrs[7] = C.ptr(x.t)
+                        bs['bs_y'] = C.ptr(x.t)
                         if xin.relu:
-                            ptrs[9], ptrs[10] = C.ptr(xin.bn.scale), C.ptr(xin.bn.shift)
+                            bs.update(bs_scale=C.ptr(xin.bn.scale), bs_shift=C.ptr(xin.bn.shift))
                     elif fuse_stats and last and xin.bn is None and id(x) in producer_sum:
                         # x is the output of a sum: gather for its first plain BatchNorm term
                         _, terms, shifts, relu_out, _o = producer_sum[id(x)]
@@ -1175,29 +1120,26 @@ class Plan(object):
                                 if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu]
                         if cand:
                             target = cand[0].act
-                            ptrs[7] = C.ptr(target.t)
-                            ptrs[8] = C.ptr(x.t) if relu_out else None
-                    store_masked = 0
+                            bs.update(bs_y=C.ptr(target.t), bs_mask=C.ptr(x.t) if relu_out else None)
                     if target is not None:
                         nrows = C.call('hrnet_conv_rows_bwdstats', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
                         rows = self._f32(nrows * 2 * x.C)
-                        ptrs[6] = C.ptr(rows)
+                        bs['stats'] = C.ptr(rows)
                         target.bwd_rows = (rows, nrows)
                         self.n_fused_bwdstats += 1
-                        if (target is not x and ptrs[8] is not None and id(x) in self._fused_out_ids
+                        if (target is not x and bs.get('bs_mask') is not None and id(x) in self._fused_out_ids
                                 and _knob('HRNET_BS_STORE_MASKED', '1') != '0'):
                             # x closes a block whose backward is a fused launch: this (last) contribution stores the
                             # gradient already multiplied by x's ReLU mask - no separate mask pass over the tensor
-                            store_masked = 1
-                    # (a backward-statistics launch is bound to the kernel family its rows buffer was sized for)
-                    route = (C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
-                             if target is not None else 0)
-                    self.bwd.add(C.OP_CONV,
-                                 ints=(self.dtid, y.N, y.H, y.W, y.C, x.H, x.W, x.C, ks, stride,
-                                       1 if stride == 2 else 0, 0, 1 if x.ginit else 0, 0, store_masked, 0, 0, route),
-                                 ptrs=ptrs)
+                            bs['bs_store_masked'] = 1
+                        # (a backward-statistics launch is bound to the kernel family its rows buffer was sized for)
+                        bs['route'] = C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
+                    self.bwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=y.N, h=y.H, w=y.W, cin=y.C, ho=x.H, wo=x.W, cout=x.C,
+                                          ks=ks, stride=stride, upz=1 if stride == 2 else 0,
+                                          accumulate=1 if x.ginit else 0, x=C.ptr(y.g), wgt=C.ptr(crec.wd), y=C.ptr(x.g),
+                                          **bs))
                     x.ginit = True
-                    if store_masked:
+                    if bs.get('bs_store_masked'):
                         x.gmasked = True
                 if lane == 0 and not in_region:
                     self._bucket_mark_after_conv(crec)
@@ -1223,14 +1165,12 @@ class Plan(object):
         if bnrec is not None and not y.bn_done and self._head_bwd is not None:
             # G = A*dz + B*y + C with dz = W3^T dHM formed again from the next layer's gradient (hrnet_head_bwd mode 2)
             ny, ncrec, relu_flag = self._head_bwd
-            b, m = y.bn, y.bn.mod
+            b = y.bn
             rows, nrows = y.bwd_rows
-            self.bwd.add(C.OP_BN_BWD_FINALIZE, ints=(nrows, y.C, 1), floats=(y.pixels,),
-                         ptrs=(C.ptr(rows), C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd),
-                               C.ptr(net.grad_of(m.weight)), C.ptr(net.grad_of(m.bias)), C.ptr(b.coef)))
-            self.bwd.add(C.OP_HEAD_BWD, ints=(self.dtid, y.N, y.H, y.W, ny.C, y.C, 2, relu_flag),
-                         ptrs=(C.ptr(ny.g), C.ptr(ncrec.wd), C.ptr(y.t), C.ptr(y.g), C.ptr(b.scale), C.ptr(b.shift),
-                               C.ptr(b.coef)))
+            self.bwd.add(self._bn_bwd_finalize_op(y, nrows, C.ptr(rows)))
+            self.bwd.add(ops.make(C.OP_HEAD_BWD, dtype=self.dtid, n=y.N, h=y.H, w=y.W, k=ny.C, cout=y.C, mode=2,
+                                  inner_relu=relu_flag, dy=C.ptr(ny.g), wt=C.ptr(ncrec.wd), y=C.ptr(y.t), out=C.ptr(y.g),
+                                  bn_scale=C.ptr(b.scale), bn_shift=C.ptr(b.shift), coef=C.ptr(b.coef)))
             y.bn_done = True
         elif bnrec is not None and not y.bn_done:
             self._bn_backward(y, C.ptr(y.g), None, 0, relu_of.get(id(y), False))
@@ -1238,15 +1178,15 @@ class Plan(object):
         if crec.mod.bias is not None and not (bnrec is not None and self.training):
             blocks = C.call('hrnet_reduce_blocks', 1, 1, y.pixels, y.C)
             self.max_bwd_part = max(self.max_bwd_part, blocks * y.C)
-            i = self.bwd.add(C.OP_BIAS_GRAD, ints=(self.dtid, y.pixels, y.C, crec.Cout, 1),
-                             ptrs=(C.ptr(y.g), C.ptr(net.grad_of(crec.mod.bias)), None))
-            self._scratch(self.bwd, i, 2, 'bwdpart')
+            i = self.bwd.add(ops.make(C.OP_BIAS_GRAD, dtype=self.dtid, pixels=y.pixels, cp=y.C, c=crec.Cout,
+                                      accumulate=1, dy=C.ptr(y.g), dbias=C.ptr(net.grad_of(crec.mod.bias))))
+            self._scratch(self.bwd, i, ops.slot(C.OP_BIAS_GRAD, 'p', 'scratch'), 'bwdpart')
         if ts:
-            ints = [self.dtid, y.N, y.H, y.W, y.C, len(ts), 1 if align else 0]
+            self.bwd.add(ops.make(C.OP_UPSAMPLE_T, dtype=self.dtid, n=y.N, h=y.H, w=y.W, c=y.C, nout=len(ts),
+                                  align=1 if align else 0, out_h=[t.H for t in ts], out_w=[t.W for t in ts],
+                                  g=C.ptr(y.g), out=[C.ptr(t.g) for t in ts]))
             for t in ts:
-                ints += [t.H, t.W]
                 t.ginit = True
-            self.bwd.add(C.OP_UPSAMPLE_T, ints=ints, ptrs=[C.ptr(y.g)] + [C.ptr(t.g) for t in ts])
         gw = net.grad_of(w)
         direct = self.batch_wred and self.wgrad_atomic
         for j, v in enumerate(vals):
@@ -1256,9 +1196,9 @@ class Plan(object):
             gptr = gw.data_ptr() + 4 * offs[j]
             # ---- weight gradient of the column slice (rows crec.Cin floats apart)
             nsplit = C.call('hrnet_wgrad_splits', self.dtid, x.N, x.H, x.W, y.C, x.C, 1, 1)
-            wints = [self.dtid, x.N, x.H, x.W, x.C, x.H, x.W, y.C, 1, 1, 0, nsplit, 1 if direct else 0, crec.Cout, cj,
-                     crec.Cin if direct else 0]
-            wptrs = [C.ptr(x.t), C.ptr(dy), None, None, None]
+            wgrad = dict(dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, ho=x.H, wo=x.W, cout=y.C, ks=1, stride=1,
+                         nsplit=nsplit, atomic=1 if direct else 0, cout_real=crec.Cout, cin_real=cj,
+                         ld=crec.Cin if direct else 0, x=C.ptr(x.t), dy=C.ptr(dy))
             side = None
             if self.offload_wgrad and lane == 0 and not in_region:
                 side = 1 + self._offload_rr % max(1, self.nlanes - 1)
@@ -1266,31 +1206,28 @@ class Plan(object):
                 self.bwd.sync(0, side)
                 self._offload_lanes.add(side)
             if direct:
-                wptrs[4] = gptr
-                self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs, lane=side)
+                self.bwd.add(ops.make(C.OP_WGRAD, slabs=gptr, **wgrad), lane=side)
             elif self.batch_wred:
                 slabs = self._f32(nsplit * y.C * x.C)
                 self.slab_bytes += slabs.numel() * 4
-                wptrs[4] = C.ptr(slabs)
                 ent = dict(slabs=C.ptr(slabs), grad=gptr, nsplit=nsplit, Cout_pad=y.C, Cin_pad=x.C, ks=1,
                            Cout=crec.Cout, Cin=cj, kflat=0, accumulate=1, ld=crec.Cin)
-                self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs, lane=side)
+                self.bwd.add(ops.make(C.OP_WGRAD, slabs=C.ptr(slabs), **wgrad), lane=side)
                 self._wred.setdefault(side if side is not None else self.bwd.lane, []).append(ent)
             else:
                 self.max_slab = max(self.max_slab, nsplit * y.C * x.C)
-                i = self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs)
-                self._scratch(self.bwd, i, 4, 'slab')
-                i = self.bwd.add(C.OP_WGRAD_REDUCE, ints=(nsplit, y.C, x.C, 1, crec.Cout, cj, 0, 1, crec.Cin),
-                                 ptrs=(None, gptr))
-                self._scratch(self.bwd, i, 0, 'slab')
+                i = self.bwd.add(ops.make(C.OP_WGRAD, **wgrad))
+                self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD, 'p', 'slabs'), 'slab')
+                i = self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=nsplit, cout_pad=y.C, cin_pad=x.C, ks=1,
+                                          cout=crec.Cout, cin=cj, accumulate=1, ld=crec.Cin, grad=gptr))
+                self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD_REDUCE, 'p', 'slabs'), 'slab')
             if side is None and lane == 0:
                 self._wred_bytes += crec.Cout * cj * 4
             # ---- input gradient: rows offs[j] .. offs[j+1] of the transposed packed weight ([Cin][Cout_pad])
             if x.g is not None:
                 wd = crec.wd.data_ptr() + offs[j] * crec.Cout_pad * self.esize
-                self.bwd.add(C.OP_CONV,
-                             ints=(self.dtid, x.N, x.H, x.W, y.C, x.H, x.W, x.C, 1, 1, 0, 0, 1 if x.ginit else 0, 0, 0),
-                             ptrs=[C.ptr(dy), wd, None, None, None, C.ptr(x.g), None, None, None, None, None])
+                self.bwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=y.C, ho=x.H, wo=x.W, cout=x.C,
+                                      ks=1, stride=1, accumulate=1 if x.ginit else 0, x=C.ptr(dy), wgt=wd, y=C.ptr(x.g)))
                 x.ginit = True
         if lane == 0 and not in_region:
             self._bucket_mark_after_conv(crec)
@@ -1407,20 +1344,17 @@ class Plan(object):
     def _bn_bwd_finalize(self, y, reduce_from=None):
         """coefficients (and dgamma/dbeta) of y's BatchNorm backward from the sums a previous launch left in
         y.bwd_rows, or from a reduction pass over the (already masked) gradient `reduce_from`"""
-        b, m = y.bn, y.bn.mod
-        tail = (C.ptr(m.weight), C.ptr(b.mean), C.ptr(b.invstd), C.ptr(self.net.grad_of(m.weight)),
-                C.ptr(self.net.grad_of(m.bias)), C.ptr(b.coef))
         if y.bwd_rows is not None:
             rows, blocks = y.bwd_rows
-            self.bwd.add(C.OP_BN_BWD_FINALIZE, ints=(blocks, y.C, 1), floats=(y.pixels,), ptrs=(C.ptr(rows),) + tail)
+            self.bwd.add(self._bn_bwd_finalize_op(y, blocks, C.ptr(rows)))
         else:
             blocks = C.call('hrnet_reduce_blocks', y.N, y.H, y.W, y.C)
             self.max_bwd_part = max(self.max_bwd_part, blocks * 2 * y.C)
-            i = self.bwd.add(C.OP_BN_BWD_REDUCE, ints=(self.dtid, y.N, y.H, y.W, y.C, 0, 0),
-                             ptrs=(None, reduce_from, None, C.ptr(y.t), None, None))
-            self._scratch(self.bwd, i, 0, 'bwdpart')
-            j = self.bwd.add(C.OP_BN_BWD_FINALIZE, ints=(blocks, y.C, 1), floats=(y.pixels,), ptrs=(None,) + tail)
-            self._scratch(self.bwd, j, 0, 'bwdpart')
+            i = self.bwd.add(ops.make(C.OP_BN_BWD_REDUCE, dtype=self.dtid, n=y.N, h=y.H, w=y.W, c=y.C, g=reduce_from,
+                                      y=C.ptr(y.t)))
+            self._scratch(self.bwd, i, ops.slot(C.OP_BN_BWD_REDUCE, 'p', 'partials'), 'bwdpart')
+            j = self.bwd.add(self._bn_bwd_finalize_op(y, blocks, None))
+            self._scratch(self.bwd, j, ops.slot(C.OP_BN_BWD_FINALIZE, 'p', 'partials'), 'bwdpart')
         y.bn_done = True
 
     def _fused_conv_bwd(self, dz, y, xin, crec, dx, addend, mask_out, rows_for, lane, reduce_from=None):
@@ -1468,14 +1402,13 @@ class Plan(object):
             rows = self._f32(ns * 2 * x.C)
             rows_for.bwd_rows = (rows, ns)
             self.n_fused_bwdstats += 1
-        self.bwd.add(kind,
-                     ints=(self.dtid, x.N, x.H, x.W, x.C, y.C, 1 if xin.relu else 0, 1 if mask_out else 0, atomic,
-                           crec.Cout, crec.Cin),
-                     ptrs=(dz, C.ptr(y.t), None if ref is not None else C.ptr(y.bn.coef), C.ptr(x.t),
-                           C.ptr(xin.bn.scale) if xin.bn else None, C.ptr(xin.bn.shift) if xin.bn else None,
-                           C.ptr(crec.wd), dx, addend, C.ptr(rows),
-                           C.ptr(rows_for.t) if rows_for is not None else None, C.ptr(slabs),
-                           ctypes.addressof(ref) if ref is not None else None))
+        self.bwd.add(ops.make(kind, dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, cout=y.C, in_relu=1 if xin.relu else 0,
+                              mask_out=1 if mask_out else 0, atomic=atomic, cout_real=crec.Cout, cin_real=crec.Cin,
+                              dz=dz, y=C.ptr(y.t), coef=None if ref is not None else C.ptr(y.bn.coef), x=C.ptr(x.t),
+                              in_scale=C.ptr(xin.bn.scale) if xin.bn else None,
+                              in_shift=C.ptr(xin.bn.shift) if xin.bn else None, wt=C.ptr(crec.wd), dx=dx, addend=addend,
+                              rows=C.ptr(rows), bs_y=C.ptr(rows_for.t) if rows_for is not None else None,
+                              slabs=C.ptr(slabs), bnref=ctypes.addressof(ref) if ref is not None else None))
         if atomic:
             if lane == 0:
                 self._wred_bytes += crec.Cout * crec.Cin * ks * ks * 4
@@ -1487,8 +1420,13 @@ class Plan(object):
             if lane == 0:
                 self._wred_bytes += crec.Cout * crec.Cin * ks * ks * 4
         else:
-            self.bwd.add(C.OP_WGRAD_REDUCE, ints=(ns, y.C, x.C, ks, crec.Cout, crec.Cin, 0, 1),
-                         ptrs=(C.ptr(slabs), C.ptr(net.grad_of(w))))
+            self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=ns, cout_pad=y.C, cin_pad=x.C, ks=ks, cout=crec.Cout,
+                                  cin=crec.Cin, accumulate=1, slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w))))
+
+    def _mask_gradient(self, out):
+        """out.g *= [out > 0], in place: the ReLU mask the fused launches expect on the gradient they read"""
+        self.bwd.add(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, dst=C.ptr(out.g),
+                              g=C.ptr(out.g), mask=C.ptr(out.t)))
 
     def _rows_target(self, x, xin):
         """the raw activation behind x whose BatchNorm backward needs (sum dz, sum dz*y) of x's gradient"""
@@ -1515,8 +1453,7 @@ class Plan(object):
             raise RuntimeError('no gradient reaches ' + out.name)
         assert not x.ginit and not y1.ginit and not y2.ginit and not y3.ginit
         if not out.gmasked:
-            self.bwd.add(C.OP_GRAD_TERM, ints=(self.dtid, out.N, out.H, out.W, out.C, 0, 0, 0, 0),
-                         ptrs=(C.ptr(out.g), C.ptr(out.g), C.ptr(out.t), None, None, None, None, None))
+            self._mask_gradient(out)
             out.gmasked = True
         residual = C.ptr(out.g)              # identity: the masked d(out) joins the input gradient of conv1
         if downsample:
@@ -1556,8 +1493,7 @@ class Plan(object):
         assert not x.ginit and not y1.ginit and not y2.ginit
         if not out.gmasked:
             # the block output's gradient came from unfused consumers: apply its ReLU mask once, in place
-            self.bwd.add(C.OP_GRAD_TERM, ints=(self.dtid, out.N, out.H, out.W, out.C, 0, 0, 0, 0),
-                         ptrs=(C.ptr(out.g), C.ptr(out.g), C.ptr(out.t), None, None, None, None, None))
+            self._mask_gradient(out)
             out.gmasked = True
         # conv2: dz = d(out) masked (it is also the identity branch's gradient); its input is relu(bn1(y1))
         self._fused_conv_bwd(C.ptr(out.g), y2, xin2, crec2, C.ptr(y1.g), None, True, y1, lane,
@@ -1592,10 +1528,10 @@ class Plan(object):
 
         def emit(entries):
             load = {l: 0.0 for l in side}
-            for wints, wptrs, ent, cost, _off in sorted(entries, key=lambda d: -d[3]):
+            for wop, ent, cost, _off in sorted(entries, key=lambda d: -d[2]):
                 l = min(side, key=lambda q: load[q])
                 load[l] += cost
-                self.bwd.add(C.OP_WGRAD, ints=wints, ptrs=wptrs, lane=l)
+                self.bwd.add(wop, lane=l)
                 if ent is not None:
                     self._wred.setdefault(l, []).append(ent)
         if self.dp_plan and _knob('HRNET_LATE_GROUPS', '1') != '0':
@@ -1621,7 +1557,7 @@ class Plan(object):
                 else:
                     bounds.append(lo_all)
             for hi_g, lo_g in zip(bounds, bounds[1:]):
-                emit([d for d in self._deferred if lo_g <= d[4] < hi_g])
+                emit([d for d in self._deferred if lo_g <= d[3] < hi_g])
                 for l in side:
                     self._flush_wred(l)
                 for l in side[1:]:
@@ -1659,7 +1595,7 @@ class Plan(object):
             block += (e['Cout'] * e['Cin'] * e['ks'] * e['ks'] + 63) // 64
         keep = self.bwd.lane
         self.bwd.lane = lane
-        i = self.bwd.add(C.OP_WGRAD_REDUCE_TABLE, ints=(len(ents), block), ptrs=(None,))
+        i = self.bwd.add(ops.make(C.OP_WGRAD_REDUCE_TABLE, n=len(ents), blocks=block))
         self.bwd.lane = keep
         self._wred_tables.append((i, ents))
         if lane == 0 or lane == self.wlane:
@@ -1682,8 +1618,9 @@ class Plan(object):
         raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
         table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
         self.keep.append(table)
+        slot = ops.slot(C.OP_WGRAD_REDUCE_TABLE, 'p', 'table')
         for i, k0 in starts:
-            self.bwd.ops[i].p[0] = C.ptr(table) + k0 * ctypes.sizeof(C.HrWredEnt)
+            self.bwd.ops[i].p[slot] = C.ptr(table) + k0 * ctypes.sizeof(C.HrWredEnt)
 
     def _resolve_scratch(self):
         sizes = {'stats': max(self.max_stats, 1), 'slab': max(self.max_slab, 1), 'bwdpart': max(self.max_bwd_part, 1)}
@@ -1714,14 +1651,14 @@ class Plan(object):
         oa, ia = self.out_act, self.inter_act
         hm = torch.empty((N, self.nj, oa.H, oa.W), dtype=torch.float32, device=self.dev)
         inter = torch.empty((N, ia.C, ia.H, ia.W), dtype=torch.float32, device=self.dev)
-        self.fwd.set_ptr(self.in_op, 0, x.data_ptr())
-        self.fwd.set_ptr(self.out_op, 1, hm.data_ptr())
-        self.fwd.set_ptr(self.inter_op, 1, inter.data_ptr())
+        self.fwd.set_ptr(self.in_op, ops.slot(C.OP_IM2COL_STEM, 'p', 'img'), x.data_ptr())
+        self.fwd.set_ptr(self.out_op, ops.slot(C.OP_NHWC_TO_NCHW, 'p', 'dst'), hm.data_ptr())
+        self.fwd.set_ptr(self.inter_op, ops.slot(C.OP_NHWC_TO_NCHW, 'p', 'dst'), inter.data_ptr())
         self.fwd.run(streams=self._side_streams())
         return hm, inter
 
     def run_backward(self, g_hm, g_inter=None, segment_hook=None):
-        self.bwd.set_ptr(self.gout_op, 0, g_hm.data_ptr())
+        self.bwd.set_ptr(self.gout_op, ops.slot(C.OP_NCHW_TO_NHWC, 'p', 'src'), g_hm.data_ptr())
         if g_inter is not None:
             # d(inter_feat) joins the gradient of stage3's branch-0 output before its consumers'
             # contributions are read: run up to that op, add it, continue

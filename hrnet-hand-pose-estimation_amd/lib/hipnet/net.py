@@ -4,6 +4,7 @@ import torch
 import torch.nn as nn
 
 from . import _capi as C
+from . import ops
 from .engine import BNRec, ConvRec, Plan, Program
 
 
@@ -132,7 +133,7 @@ class HipNet(object):
         table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         self._tables = getattr(self, '_tables', []) + [table]
         prog = Program()
-        prog.add(C.OP_PACK_TABLE, ints=(self.dtid, len(items), block), ptrs=(C.ptr(table),))
+        prog.add(ops.make(C.OP_PACK_TABLE, dtype=self.dtid, n=len(items), blocks=block, table=C.ptr(table)))
         return prog.finalize()
 
     def head_slices(self, crec, widths):

@@ -39,21 +39,15 @@ enum {
   HR_E_BADOP = -3     /* unknown op kind in a program */
 };
 
-/* ---- op kinds of a recorded program (hrnet_program_run) -------------------------------- */
+/* ---- op kinds of a recorded program (hrnet_program_run); the slots of each kind are named below ------ */
 enum {
-  HR_OP_CONV = 1,          /* conv / dgrad (implicit GEMM, MFMA); a backward-statistics op may set i[14] = 1: the
-                              stored gradient is dz = v * [mask > 0] (what the fused backward launches expect) */
-  HR_OP_WGRAD = 2,         /* weight gradient partial slabs; i[12] = 1: p[4] is the OIHW f32 gradient itself
-                              ([i[13] = real Cout][i[14] = real Cin][ks][ks]) and every workgroup ADDS its tile into it with
-                              float atomics - no slabs, no reduce launch, not bit-reproducible. HR_OP_BWD_FUSED / HR_OP_BWD_PW
-                              take the same switch in i[8] (gradient in p[11], real Cout / Cin in i[9] / i[10]) */
+  HR_OP_CONV = 1,          /* conv / dgrad (implicit GEMM, MFMA) */
+  HR_OP_WGRAD = 2,         /* weight gradient: partial slabs, or float atomics into the gradient */
   HR_OP_WGRAD_REDUCE = 3,  /* slabs -> OIHW f32 gradient */
   HR_OP_BN_FINALIZE = 4,   /* stat partials -> scale/shift (+ running stats) */
   HR_OP_SUM_TERMS = 5,     /* out = relu(sum_t relu_t(affine_t(up_t(src_t)))) */
   HR_OP_GRAD_TERM = 6,     /* dst (+)= A*pool(g*mask) + B*y + C */
-  HR_OP_BN_BWD_REDUCE = 7, /* per-channel sum(dz), sum(dz*y) partials; p[6] (optional): dz itself (pooled, masked,
-                              [N,H,W,C] in the compute dtype) stored for the apply pass, which then runs
-                              HR_OP_GRAD_TERM with g = that tensor, sh = 0 and no masks (in place) */
+  HR_OP_BN_BWD_REDUCE = 7, /* per-channel sum(dz), sum(dz*y) partials */
   HR_OP_BN_BWD_FINALIZE = 8,
   HR_OP_BILINEAR_CAT = 9,
   HR_OP_BILINEAR_CAT_BWD = 10,
@@ -64,40 +58,199 @@ enum {
   HR_OP_BIAS_GRAD = 15,
   HR_OP_FILL = 16,
   HR_OP_PACK_TABLE = 17,
-  HR_OP_EVENT_RECORD = 18, /* p[0] = event, recorded on the op's lane */
-  HR_OP_STREAM_WAIT = 19,  /* p[0] = event, the op's lane waits for it */
-  HR_OP_WGRAD_REDUCE_TABLE = 20, /* p[0] = device HrWredEnt table, i[0] = n, i[1] = total blocks */
+  HR_OP_EVENT_RECORD = 18,
+  HR_OP_STREAM_WAIT = 19,
+  HR_OP_WGRAD_REDUCE_TABLE = 20,
   HR_OP_BWD_FUSED = 21,    /* hrnet_conv3x3_bwd_fused */
-  HR_OP_BN_FINALIZE_TABLE = 22, /* p[0] = device HrBnEnt table, i[0] = n, i[1] = total blocks */
-  HR_OP_BWD_PW = 23,       /* hrnet_conv1x1_bwd_fused (slots as HR_OP_BWD_FUSED) */
+  HR_OP_BN_FINALIZE_TABLE = 22,
+  HR_OP_BWD_PW = 23,       /* hrnet_conv1x1_bwd_fused */
   HR_OP_CONV_SUM = 24,     /* hrnet_conv2d_sum */
-  HR_OP_EW_TABLE = 25,     /* several HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE / HR_OP_SUM_TERMS jobs as
-                              ONE launch (HR_OP_SUM_TERMS: i[4] = 1 if a job's BatchNorm is given as batch sums, and a
-                              job carries its eps bits in i[18] instead of i[16]):
-                              p[0] = device array of HrOp jobs (slots as for the single op; i[16] = first block of the
-                              job, i[17] = its blocks: hrnet_ew_table_blocks()), i[0] = jobs, i[1] = total blocks,
-                              i[2] = kind of the jobs, i[3] = dtype */
-  HR_OP_HEAD_MIX = 26,     /* hrnet_head_mix: i = {dtype, N, H, W, C0, Cout, nup, align, h1, w1, h2, w2, h3, w3, rows
-                              mode}, p = {x0, w0 packed, bias, y, statistics, t1, t2, t3} */
-  HR_OP_HEAD_BWD = 28,     /* hrnet_head_bwd: i = {dtype, N, H, W, K, Cout, mode, inner_relu}, p = {dY, wT, y, out, bn scale,
-                              bn shift, coef} */
-  HR_OP_POOL_REDUCE = 29,  /* the BatchNorm-backward reduction of up to three nearest-up-sampled terms of one fuse sum
-                              (pose_hrnet.py:257-264) in ONE walk over the sum's gradient: i = {dtype, N, H, W, C,
-                              nlev}, p = {g, mask, y1, dz1, partials1, y2, dz2, partials2, y3, dz3, partials3}; level
-                              l pools 2^l x 2^l blocks; dz_l is stored for the apply pass (HR_OP_GRAD_TERM with g =
-                              dz_l, sh = 0); partials_l[hrnet_reduce_blocks(N, H / 2, W / 2, C)][2][C] */
-  HR_OP_UPSAMPLE_T = 27    /* hrnet_upsample_bilinear_t: i = {dtype, N, H, W, C, nout, align, h1, w1, h2, w2, h3, w3,
-                              streamed}, p = {G, out1, out2, out3} */
+  HR_OP_EW_TABLE = 25,     /* several element-wise jobs of one kind as ONE launch */
+  HR_OP_HEAD_MIX = 26,     /* hrnet_head_mix */
+  HR_OP_UPSAMPLE_T = 27,   /* hrnet_upsample_bilinear_t */
+  HR_OP_HEAD_BWD = 28,     /* hrnet_head_bwd */
+  HR_OP_POOL_REDUCE = 29   /* pooled BatchNorm-backward reduction of the up-sampled terms of a fuse sum */
 };
 
-/* One recorded op: integer / float / pointer slots, meaning per kind (see the
- * hrnet_* function of the same name; slots are filled in argument order). */
+/* One recorded op: integer / float / pointer slots. What a slot means depends on the kind: the enums below name
+ * every slot, HR_<table>_I_* indexing i[], HR_<table>_F_* f[] and HR_<table>_P_* p[] (an argument of the hrnet_*
+ * function a table cites keeps that argument's meaning). Kinds that share a layout share a table. A name ending in
+ * 0 or 1 is the first member of an indexed family. i[HR_LANE_SLOT] belongs to the runner, not to any kind. */
 typedef struct HrOp {
   int32_t kind;
   int32_t i[19];
   float f[4];
   void* p[14];
 } HrOp;
+#define HR_LANE_SLOT 18
+
+/* slots of HR_OP_CONV: hrnet_conv2d / _bnref / _bwdstats. BS_* (p) make it a backward-statistics launch; such an op
+ * may set BS_STORE_MASKED = 1: the stored gradient is dz = v * [mask > 0] (what the fused backward launches expect).
+ * IN_DY / IN_DX: displacement of the input window of a 1x1 stride-1 launch (hrnet_conv2d_dilated3x3). ROUTE: the
+ * kernel family a recorded backward-statistics launch is bound to (hrnet_conv_route(); 0 = decide at launch).
+ * STATS_ATOMIC = 1: STATS is sums[8][2][Cout], added to with float atomics. IN_SUMS / IN_GAMMA / IN_BETA /
+ * IN_INV_COUNT / IN_EPS give the input's BatchNorm as batch sums instead of IN_SCALE / IN_SHIFT (hrnet_conv2d_bnref) */
+enum { HR_CONV_I_DTYPE = 0, HR_CONV_I_N, HR_CONV_I_H, HR_CONV_I_W, HR_CONV_I_CIN, HR_CONV_I_HO, HR_CONV_I_WO,
+       HR_CONV_I_COUT, HR_CONV_I_KS, HR_CONV_I_STRIDE, HR_CONV_I_UPZ, HR_CONV_I_IN_RELU, HR_CONV_I_ACCUMULATE,
+       HR_CONV_I_STATS_ATOMIC, HR_CONV_I_BS_STORE_MASKED, HR_CONV_I_IN_DY, HR_CONV_I_IN_DX, HR_CONV_I_ROUTE };
+enum { HR_CONV_F_IN_INV_COUNT = 0, HR_CONV_F_IN_EPS };
+enum { HR_CONV_P_X = 0, HR_CONV_P_WGT, HR_CONV_P_IN_SCALE, HR_CONV_P_IN_SHIFT, HR_CONV_P_BIAS, HR_CONV_P_Y,
+       HR_CONV_P_STATS, HR_CONV_P_BS_Y, HR_CONV_P_BS_MASK, HR_CONV_P_BS_SCALE, HR_CONV_P_BS_SHIFT, HR_CONV_P_IN_SUMS,
+       HR_CONV_P_IN_GAMMA, HR_CONV_P_IN_BETA };
+
+/* slots of HR_OP_WGRAD: hrnet_conv2d_wgrad. ATOMIC = 1: SLABS is the OIHW f32 gradient itself
+ * ([COUT_REAL][CIN_REAL][ks][ks]) and every workgroup ADDS its tile into it with float atomics - no slabs, no reduce
+ * launch, not bit-reproducible; LD (1x1 only): floats between consecutive output-channel rows of that gradient (a
+ * column slice of a wider weight), 0 = CIN_REAL */
+enum { HR_WGRAD_I_DTYPE = 0, HR_WGRAD_I_N, HR_WGRAD_I_H, HR_WGRAD_I_W, HR_WGRAD_I_CIN, HR_WGRAD_I_HO, HR_WGRAD_I_WO,
+       HR_WGRAD_I_COUT, HR_WGRAD_I_KS, HR_WGRAD_I_STRIDE, HR_WGRAD_I_IN_RELU, HR_WGRAD_I_NSPLIT, HR_WGRAD_I_ATOMIC,
+       HR_WGRAD_I_COUT_REAL, HR_WGRAD_I_CIN_REAL, HR_WGRAD_I_LD };
+enum { HR_WGRAD_P_X = 0, HR_WGRAD_P_DY, HR_WGRAD_P_IN_SCALE, HR_WGRAD_P_IN_SHIFT, HR_WGRAD_P_SLABS };
+
+/* slots of HR_OP_WGRAD_REDUCE: hrnet_wgrad_reduce; LD as HrWredEnt.ld */
+enum { HR_WGRAD_REDUCE_I_NSPLIT = 0, HR_WGRAD_REDUCE_I_COUT_PAD, HR_WGRAD_REDUCE_I_CIN_PAD, HR_WGRAD_REDUCE_I_KS,
+       HR_WGRAD_REDUCE_I_COUT, HR_WGRAD_REDUCE_I_CIN, HR_WGRAD_REDUCE_I_KFLAT, HR_WGRAD_REDUCE_I_ACCUMULATE,
+       HR_WGRAD_REDUCE_I_LD };
+enum { HR_WGRAD_REDUCE_P_SLABS = 0, HR_WGRAD_REDUCE_P_GRAD };
+
+/* slots of HR_OP_BN_FINALIZE: hrnet_bn_finalize */
+enum { HR_BN_FINALIZE_I_TILES = 0, HR_BN_FINALIZE_I_C, HR_BN_FINALIZE_I_TRAINING };
+enum { HR_BN_FINALIZE_F_COUNT = 0, HR_BN_FINALIZE_F_MOMENTUM, HR_BN_FINALIZE_F_EPS };
+enum { HR_BN_FINALIZE_P_STATS = 0, HR_BN_FINALIZE_P_GAMMA, HR_BN_FINALIZE_P_BETA, HR_BN_FINALIZE_P_RUNNING_MEAN,
+       HR_BN_FINALIZE_P_RUNNING_VAR, HR_BN_FINALIZE_P_NUM_BATCHES_TRACKED, HR_BN_FINALIZE_P_SCALE,
+       HR_BN_FINALIZE_P_SHIFT, HR_BN_FINALIZE_P_SAVE_MEAN, HR_BN_FINALIZE_P_SAVE_INVSTD };
+
+/* slots of HR_OP_SUM_TERMS: hrnet_sum_terms / hrnet_sum_terms_bnref; term t < 4 sits at <NAME>0 + t. SUMS_MODE: bit
+ * t set = term t's BatchNorm is given as batch sums (SCALE0 + t = sums, SHIFT0 + t = gamma, INV_COUNT0 + t = 1 /
+ * count), EPS_BITS = the bits of the f32 eps */
+enum { HR_SUM_I_DTYPE = 0, HR_SUM_I_N, HR_SUM_I_H, HR_SUM_I_W, HR_SUM_I_C, HR_SUM_I_NTERMS, HR_SUM_I_RELU_OUT,
+       HR_SUM_I_SH0, HR_SUM_I_RELU0 = 11, HR_SUM_I_SUMS_MODE = 15, HR_SUM_I_EPS_BITS };
+enum { HR_SUM_F_INV_COUNT0 = 0 };
+enum { HR_SUM_P_OUT = 0, HR_SUM_P_SRC0, HR_SUM_P_SCALE0 = 5, HR_SUM_P_SHIFT0 = 9 };
+
+/* slots of HR_OP_GRAD_TERM: hrnet_grad_term and hrnet_grad_term2 (the latter: SH = INNER_RELU = 0, plus DST2 /
+ * ACCUMULATE2) */
+enum { HR_GRAD_TERM_I_DTYPE = 0, HR_GRAD_TERM_I_N, HR_GRAD_TERM_I_H, HR_GRAD_TERM_I_W, HR_GRAD_TERM_I_C,
+       HR_GRAD_TERM_I_SH, HR_GRAD_TERM_I_INNER_RELU, HR_GRAD_TERM_I_ACCUMULATE, HR_GRAD_TERM_I_ACCUMULATE2 };
+enum { HR_GRAD_TERM_P_DST = 0, HR_GRAD_TERM_P_G, HR_GRAD_TERM_P_MASK, HR_GRAD_TERM_P_Y, HR_GRAD_TERM_P_SCALE,
+       HR_GRAD_TERM_P_SHIFT, HR_GRAD_TERM_P_COEF, HR_GRAD_TERM_P_DST2 };
+
+/* slots of HR_OP_BN_BWD_REDUCE: hrnet_bn_bwd_reduce. DZ (optional): dz itself (pooled, masked, [N,H,W,C] in the
+ * compute dtype) stored for the apply pass, which then runs HR_OP_GRAD_TERM with g = that tensor, sh = 0 and no
+ * masks (in place). Slots 0..5 of both arrays mean what they mean in HR_OP_GRAD_TERM (one decoder reads both kinds) */
+enum { HR_BN_BWD_REDUCE_I_DTYPE = 0, HR_BN_BWD_REDUCE_I_N, HR_BN_BWD_REDUCE_I_H, HR_BN_BWD_REDUCE_I_W,
+       HR_BN_BWD_REDUCE_I_C, HR_BN_BWD_REDUCE_I_SH, HR_BN_BWD_REDUCE_I_INNER_RELU };
+enum { HR_BN_BWD_REDUCE_P_PARTIALS = 0, HR_BN_BWD_REDUCE_P_G, HR_BN_BWD_REDUCE_P_MASK, HR_BN_BWD_REDUCE_P_Y,
+       HR_BN_BWD_REDUCE_P_SCALE, HR_BN_BWD_REDUCE_P_SHIFT, HR_BN_BWD_REDUCE_P_DZ };
+
+/* slots of HR_OP_BN_BWD_FINALIZE: hrnet_bn_bwd_finalize */
+enum { HR_BN_BWD_FINALIZE_I_BLOCKS = 0, HR_BN_BWD_FINALIZE_I_C, HR_BN_BWD_FINALIZE_I_ACCUMULATE };
+enum { HR_BN_BWD_FINALIZE_F_COUNT = 0 };
+enum { HR_BN_BWD_FINALIZE_P_PARTIALS = 0, HR_BN_BWD_FINALIZE_P_GAMMA, HR_BN_BWD_FINALIZE_P_SAVE_MEAN,
+       HR_BN_BWD_FINALIZE_P_SAVE_INVSTD, HR_BN_BWD_FINALIZE_P_DGAMMA, HR_BN_BWD_FINALIZE_P_DBETA,
+       HR_BN_BWD_FINALIZE_P_COEF };
+
+/* slots of HR_OP_BILINEAR_CAT, HR_OP_BILINEAR_CAT_BWD: hrnet_bilinear_cat / hrnet_bilinear_cat_bwd; branch k < 4 at
+ * <NAME>0 + k. ALIGN (a float: != 0 = align_corners); ACCUMULATE: backward only; CAT = the concat (forward) or its
+ * gradient, X0 + k = branch k (forward) or its gradient */
+enum { HR_CAT_I_DTYPE = 0, HR_CAT_I_NBR, HR_CAT_I_N, HR_CAT_I_H, HR_CAT_I_W, HR_CAT_I_HS0, HR_CAT_I_WS0 = 9,
+       HR_CAT_I_CS0 = 13, HR_CAT_I_ACCUMULATE = 17 };
+enum { HR_CAT_F_ALIGN = 0 };
+enum { HR_CAT_P_CAT = 0, HR_CAT_P_X0 };
+
+/* slots of HR_OP_IM2COL_STEM: hrnet_im2col_stem */
+enum { HR_IM2COL_I_DTYPE = 0, HR_IM2COL_I_N, HR_IM2COL_I_C, HR_IM2COL_I_H, HR_IM2COL_I_W, HR_IM2COL_I_HO,
+       HR_IM2COL_I_WO, HR_IM2COL_I_KPAD };
+enum { HR_IM2COL_P_IMG = 0, HR_IM2COL_P_COLS };
+
+/* slots of HR_OP_NHWC_TO_NCHW, HR_OP_NCHW_TO_NHWC: hrnet_nhwc_to_nchw / hrnet_nchw_to_nhwc */
+enum { HR_LAYOUT_I_DTYPE = 0, HR_LAYOUT_I_N, HR_LAYOUT_I_H, HR_LAYOUT_I_W, HR_LAYOUT_I_CP, HR_LAYOUT_I_C };
+enum { HR_LAYOUT_P_SRC = 0, HR_LAYOUT_P_DST };
+
+/* slots of HR_OP_PACK_WEIGHTS: hrnet_pack_weights */
+enum { HR_PACK_I_DTYPE = 0, HR_PACK_I_COUT, HR_PACK_I_CIN, HR_PACK_I_KS, HR_PACK_I_COUT_PAD, HR_PACK_I_CIN_PAD,
+       HR_PACK_I_MODE };
+enum { HR_PACK_P_SRC = 0, HR_PACK_P_PACKED };
+
+/* slots of HR_OP_BIAS_GRAD: hrnet_bias_grad */
+enum { HR_BIAS_GRAD_I_DTYPE = 0, HR_BIAS_GRAD_I_PIXELS, HR_BIAS_GRAD_I_CP, HR_BIAS_GRAD_I_C,
+       HR_BIAS_GRAD_I_ACCUMULATE };
+enum { HR_BIAS_GRAD_P_DY = 0, HR_BIAS_GRAD_P_DBIAS, HR_BIAS_GRAD_P_SCRATCH };
+
+/* slots of HR_OP_FILL: hrnet_fill_zero: the byte count as two 32-bit halves */
+enum { HR_FILL_I_BYTES_LO = 0, HR_FILL_I_BYTES_HI };
+enum { HR_FILL_P_DST = 0 };
+
+/* slots of HR_OP_PACK_TABLE: hrnet_pack_weights_table (TABLE: device HrPackEnt[N]) */
+enum { HR_PACK_TABLE_I_DTYPE = 0, HR_PACK_TABLE_I_N, HR_PACK_TABLE_I_BLOCKS };
+enum { HR_PACK_TABLE_P_TABLE = 0 };
+
+/* slots of HR_OP_EVENT_RECORD, HR_OP_STREAM_WAIT: EVENT (from hrnet_event_create) is recorded on the op's lane / the
+ * op's lane waits for it */
+enum { HR_EVENT_P_EVENT = 0 };
+
+/* slots of HR_OP_WGRAD_REDUCE_TABLE, HR_OP_BN_FINALIZE_TABLE: hrnet_wgrad_reduce_table (TABLE: device HrWredEnt[N])
+ * / hrnet_bn_finalize_table (device HrBnEnt[N]); BLOCKS = total blocks */
+enum { HR_TABLE_I_N = 0, HR_TABLE_I_BLOCKS };
+enum { HR_TABLE_P_TABLE = 0 };
+
+/* slots of HR_OP_BWD_FUSED, HR_OP_BWD_PW: hrnet_conv3x3_bwd_fused / hrnet_conv1x1_bwd_fused (HR_OP_BWD_PW: pixels =
+ * N * H * W). BNREF: HOST pointer to a HrBnBwdRef kept alive by the caller, or NULL. ATOMIC = 1: SLABS is the OIHW
+ * gradient the weight-gradient tiles are ADDED to (float atomics), COUT_REAL / CIN_REAL its extents (HR_OP_BWD_PW:
+ * they must equal the tensors') */
+enum { HR_BWD_FUSED_I_DTYPE = 0, HR_BWD_FUSED_I_N, HR_BWD_FUSED_I_H, HR_BWD_FUSED_I_W, HR_BWD_FUSED_I_CIN,
+       HR_BWD_FUSED_I_COUT, HR_BWD_FUSED_I_IN_RELU, HR_BWD_FUSED_I_MASK_OUT, HR_BWD_FUSED_I_ATOMIC,
+       HR_BWD_FUSED_I_COUT_REAL, HR_BWD_FUSED_I_CIN_REAL };
+enum { HR_BWD_FUSED_P_DZ = 0, HR_BWD_FUSED_P_Y, HR_BWD_FUSED_P_COEF, HR_BWD_FUSED_P_X, HR_BWD_FUSED_P_IN_SCALE,
+       HR_BWD_FUSED_P_IN_SHIFT, HR_BWD_FUSED_P_WT, HR_BWD_FUSED_P_DX, HR_BWD_FUSED_P_ADDEND, HR_BWD_FUSED_P_ROWS,
+       HR_BWD_FUSED_P_BS_Y, HR_BWD_FUSED_P_SLABS, HR_BWD_FUSED_P_BNREF };
+
+/* slots of HR_OP_CONV_SUM: hrnet_conv2d_sum */
+enum { HR_CONV_SUM_I_DTYPE = 0, HR_CONV_SUM_I_N, HR_CONV_SUM_I_H, HR_CONV_SUM_I_W, HR_CONV_SUM_I_CIN,
+       HR_CONV_SUM_I_COUT, HR_CONV_SUM_I_KS, HR_CONV_SUM_I_STATS_ATOMIC };
+enum { HR_CONV_SUM_F_IN_INV_COUNT = 0, HR_CONV_SUM_F_IN_EPS };
+enum { HR_CONV_SUM_P_X = 0, HR_CONV_SUM_P_WGT, HR_CONV_SUM_P_IN_SCALE, HR_CONV_SUM_P_IN_SHIFT, HR_CONV_SUM_P_IN_SUMS,
+       HR_CONV_SUM_P_IN_GAMMA, HR_CONV_SUM_P_IN_BETA, HR_CONV_SUM_P_Y, HR_CONV_SUM_P_STATS, HR_CONV_SUM_P_X2,
+       HR_CONV_SUM_P_SIDE };
+
+/* slots of HR_OP_EW_TABLE: several HR_OP_GRAD_TERM / HR_OP_BN_BWD_REDUCE / HR_OP_BN_BWD_FINALIZE / HR_OP_POOL_REDUCE
+ * / HR_OP_SUM_TERMS jobs as ONE launch. TABLE: device array of JOBS HrOp records of kind KIND (slots as for the
+ * single op, plus HR_EWJOB_* below); BLOCKS = total blocks; SUMS (HR_OP_SUM_TERMS) = 1 if some job's BatchNorm is
+ * given as batch sums */
+enum { HR_EW_TABLE_I_JOBS = 0, HR_EW_TABLE_I_BLOCKS, HR_EW_TABLE_I_KIND, HR_EW_TABLE_I_DTYPE, HR_EW_TABLE_I_SUMS };
+enum { HR_EW_TABLE_P_TABLE = 0 };
+
+/* slots of HR_OP_HEAD_MIX: hrnet_head_mix; up-sampled term k < 3: UP_H1 + 2 * k, UP_W1 + 2 * k, T1 + k */
+enum { HR_HEAD_MIX_I_DTYPE = 0, HR_HEAD_MIX_I_N, HR_HEAD_MIX_I_H, HR_HEAD_MIX_I_W, HR_HEAD_MIX_I_C0,
+       HR_HEAD_MIX_I_COUT, HR_HEAD_MIX_I_NUP, HR_HEAD_MIX_I_ALIGN, HR_HEAD_MIX_I_UP_H1, HR_HEAD_MIX_I_UP_W1,
+       HR_HEAD_MIX_I_ROWS_MODE = 14 };
+enum { HR_HEAD_MIX_P_X0 = 0, HR_HEAD_MIX_P_W0, HR_HEAD_MIX_P_BIAS, HR_HEAD_MIX_P_Y, HR_HEAD_MIX_P_STATS,
+       HR_HEAD_MIX_P_T1 };
+
+/* slots of HR_OP_UPSAMPLE_T: hrnet_upsample_bilinear_t; output k < 3: OUT_H1 + 2 * k, OUT_W1 + 2 * k, OUT1 + k */
+enum { HR_UPSAMPLE_T_I_DTYPE = 0, HR_UPSAMPLE_T_I_N, HR_UPSAMPLE_T_I_H, HR_UPSAMPLE_T_I_W, HR_UPSAMPLE_T_I_C,
+       HR_UPSAMPLE_T_I_NOUT, HR_UPSAMPLE_T_I_ALIGN, HR_UPSAMPLE_T_I_OUT_H1, HR_UPSAMPLE_T_I_OUT_W1,
+       HR_UPSAMPLE_T_I_STREAMED = 13 };
+enum { HR_UPSAMPLE_T_P_G = 0, HR_UPSAMPLE_T_P_OUT1 };
+
+/* slots of HR_OP_HEAD_BWD: hrnet_head_bwd */
+enum { HR_HEAD_BWD_I_DTYPE = 0, HR_HEAD_BWD_I_N, HR_HEAD_BWD_I_H, HR_HEAD_BWD_I_W, HR_HEAD_BWD_I_K,
+       HR_HEAD_BWD_I_COUT, HR_HEAD_BWD_I_MODE, HR_HEAD_BWD_I_INNER_RELU };
+enum { HR_HEAD_BWD_P_DY = 0, HR_HEAD_BWD_P_WT, HR_HEAD_BWD_P_Y, HR_HEAD_BWD_P_OUT, HR_HEAD_BWD_P_BN_SCALE,
+       HR_HEAD_BWD_P_BN_SHIFT, HR_HEAD_BWD_P_COEF };
+
+/* slots of HR_OP_POOL_REDUCE: the BatchNorm-backward reduction of up to three nearest-up-sampled terms of one fuse
+ * sum (pose_hrnet.py:257-264) in ONE walk over the sum's gradient G: level l < NLEV pools 2^(l+1) x 2^(l+1) blocks
+ * and sits at Y0 / DZ0 / PARTIALS0 + 3 * l; dz_l is stored for the apply pass (HR_OP_GRAD_TERM with g = dz_l, sh =
+ * 0); partials_l[hrnet_reduce_blocks(N, H / 2, W / 2, C)][2][C] */
+enum { HR_POOL_I_DTYPE = 0, HR_POOL_I_N, HR_POOL_I_H, HR_POOL_I_W, HR_POOL_I_C, HR_POOL_I_NLEV };
+enum { HR_POOL_P_G = 0, HR_POOL_P_MASK, HR_POOL_P_Y0, HR_POOL_P_DZ0, HR_POOL_P_PARTIALS0 };
+
+/* A job of a HR_OP_EW_TABLE launch is an HrOp of the jobs' kind in the device table with its block range laid over
+ * it: blocks [BLOCK0, BLOCK0 + BLOCKS) of the launch are the job's (BLOCKS = hrnet_ew_table_blocks()). No table of a
+ * kind that can be a job names these two slots - except HR_SUM_I_EPS_BITS, which a sum job therefore carries in
+ * SUM_EPS_BITS instead (a job has no lane). */
+enum { HR_EWJOB_I_BLOCK0 = 16, HR_EWJOB_I_BLOCKS = 17, HR_EWJOB_I_SUM_EPS_BITS = 18 };
 
 const char* hrnet_last_error_string(void);
 int hrnet_abi_version(void);
@@ -110,7 +263,6 @@ int hrnet_ew_table_blocks(int kind, int dtype, int N, int H, int W, int C);
  * HR_OP_STREAM_WAIT ops express the dependencies between lanes (independent branches of a
  * HighResolutionModule, weight-gradient work off the critical path). Events come from
  * hrnet_event_create (host-side handles; no device memory). */
-#define HR_LANE_SLOT 18
 int hrnet_program_run_streams(const HrOp* ops, int n, const hr_stream_t* streams, int nstreams);
 /* Measurement form of the above: a timing event behind every op on its lane; end_ms[k] = completion of op k in
  * ms since the call began on op 0's lane. Synchronises every stream before returning (not for the training loop). */
@@ -182,7 +334,7 @@ int hrnet_conv_ring_supported(int dtype, int N, int H, int W, int Cin, int Cout)
 /* statistics rows hrnet_conv2d_bwdstats leaves for a launch of this shape (hrnet_conv_tiles_bwdstats() for the
  * tile-walking body; the pixel walks of the LDS-ring grid where that serves the launch) */
 int hrnet_conv_rows_bwdstats(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);
-/* kernel family a RECORDED backward-statistics launch of this shape is bound to (HR_OP_CONV i[17]): 2 = LDS ring,
+/* kernel family a RECORDED backward-statistics launch of this shape is bound to (HR_CONV_I_ROUTE): 2 = LDS ring,
  * 1 = tile-walking body; the rows buffer above is sized for that family, so the op keeps the decision and a later
  * hrnet_conv_ring_enable() cannot change how many rows the launch writes (it fails instead). 0 = decide at launch. */
 int hrnet_conv_route(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);

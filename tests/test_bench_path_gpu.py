@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from spawned import spawned
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -572,3 +574,57 @@ def test_fused_backward_matches_unfused_backward(dtype, monkeypatch):
         assert cos >= 0.999999 and errs[-1][0] <= 2e-3 and float(np.median([e[0] for e in errs])) <= 1e-4
     else:
         assert cos >= 0.999 and errs[-1][0] <= 0.15 and float(np.median([e[0] for e in errs])) <= 1.5e-2
+
+
+# ---- every slot a recorded program sets is one its kind's table names (include/hrnet_hip.h, hipnet.ops.SLOTS) ----
+def _unnamed_slots(op, job=False):
+    """the non-zero slots of a recorded op (or of a job of a table-driven launch) that its kind's table does not name"""
+    from hipnet import _capi as C
+    from hipnet import ops
+    kind = int(op.kind)
+    named = {arr: set() for arr in 'ifp'}
+    for arr in 'ifp':
+        for name, idx in ops.SLOTS[kind][arr].items():
+            stride, count = ops.FAMILIES.get((ops.PREFIX[kind], arr, name), (0, 1))
+            if not (job and name in ops.JOB_MOVES.get(kind, {})):
+                named[arr].update(idx + stride * k for k in range(count))
+    if job:
+        named['i'].update(ops.EWJOB[j] for j in ['BLOCK0', 'BLOCKS'] + list(ops.JOB_MOVES.get(kind, {}).values()))
+    else:
+        named['i'].add(C.LANE_SLOT)
+    return [(kind, arr, k) for arr in 'ifp' for k, v in enumerate(getattr(op, arr)) if v and k not in named[arr]]
+
+
+def _recorded_slots_are_named():
+    from hipnet import _capi as C
+    model, _ = _model('bf16')
+    plan = model.train().hip().plan(1, 64, 64, True, True)        # recorded, not run
+    assert len(plan.fwd) > 300 and len(plan.bwd) > 300
+    bad, kinds, njobs = [], set(), 0
+    for prog in (plan.fwd, plan.bwd):
+        for op in prog.ops:
+            kinds.add(int(op.kind))
+            bad += _unnamed_slots(op)
+            if int(op.kind) == C.OP_EW_TABLE:
+                jobs = _table_jobs(op, plan, C)
+                assert jobs and all(int(j.kind) == op.i[2] for j in jobs)
+                njobs += len(jobs)
+                for j in jobs:
+                    bad += _unnamed_slots(j, job=True)
+    assert not bad, sorted(set(bad))
+    assert njobs > 0 and {C.OP_CONV, C.OP_WGRAD, C.OP_SUM_TERMS, C.OP_GRAD_TERM, C.OP_HEAD_MIX} <= kinds
+    return kinds
+
+
+def test_recorded_programs_set_only_named_slots():
+    from hipnet import _capi as C
+    kinds = _recorded_slots_are_named()
+    assert C.OP_BN_FINALIZE_TABLE in kinds and C.OP_BN_FINALIZE not in kinds        # batch sums, atomics
+
+
+@spawned
+def test_recorded_programs_set_only_named_slots_deterministic():
+    from hipnet import _capi as C
+    os.environ['HRNET_DETERMINISTIC'] = '1'
+    kinds = _recorded_slots_are_named()
+    assert C.OP_BN_FINALIZE in kinds and C.OP_WGRAD_REDUCE_TABLE in kinds           # rows + finalize launches, slabs
