@@ -850,6 +850,38 @@ int hrnet_volumetric_ce_loss_bwd(const float* p, const float* validity, const in
                                  int B, int J, int X, int Y, int Z, hr_stream_t stream);
 
 /*
+ * V2V inference (reference lib/models/v2v.py; called from lib/models/triangulation.py:349,467): the 3-D convolutions
+ * of the volumetric models, eval-mode forward, f32 only (HR_BF16 is refused; the dtype argument is there so that bf16
+ * can be added without an ABI change). Activations are NDHWC f32, element offsets 64-bit; Cin % 4 == 0 and
+ * Cout % 16 == 0, pad channels zero. Stream-ordered, no allocation, no host synchronisation, no atomics: a call is
+ * bit-reproducible. No dynamic LDS, so no function attribute is touched and every entry may be captured at once.
+ *
+ * conv3d: Conv3d(ks, stride 1, padding ks / 2), ks = 1 | 3 | 7 (v2v.py:11,24,27,35,160), any N, D, H, W >= 1, on the
+ *   exact-f32 MFMA. w_packed [ks^3][Cout][Cin] from pack_weights3d. Epilogue on the f32 accumulator, in this order:
+ *   acc * scale[c] + shift[c] (one fmaf; scale NULL = 1), + res[n,d,h,w,c] if res != NULL, ReLU if relu != 0: the
+ *   eval-mode BatchNorm3d (v2v.py:12,25,28,36) with scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) * scale
+ *   built by the host in f64, the relu(res + skip) of Res3DBlock (v2v.py:39-42), and the bare output layer (shift = bias).
+ * pack_weights3d: Conv3d's OIDHW [Cout][Cin][ks][ks][ks], or with transposed != 0 ConvTranspose3d's IODHW
+ *   [Cin][Cout][ks][ks][ks], to [ks^3][Cout_pad][Cin_pad] with zeros in the pads. ks = 2 is the deconvolution's.
+ * maxpool3d: F.max_pool3d(x, 2, 2) (v2v.py:50-51): y [N,D/2,H/2,W/2,C]; D, H and W must be even (HR_E_BADARG if not),
+ *   C % 4 == 0.
+ * deconv3d_k2s2: ConvTranspose3d(k = 2, s = 2) (v2v.py:60): x [N,D,H,W,Cin] -> y [N,2D,2H,2W,Cout],
+ *   y[n,2d+a,2h+b,2w+c,:] = W[:,:,a,b,c]^T x[n,d,h,w,:]; w_packed [8][Cout][Cin]. Epilogue: acc * scale + shift, ReLU if
+ *   relu != 0, THEN + add[n,.,.,.,c] if add != NULL - the decoder's x = upsample(x) + skip_x (v2v.py:123-136).
+ * conv3d_supported: 1 if conv3d serves (dtype, Cin, Cout, ks), else 0. Pure host query, no error code.
+ */
+int hrnet_conv3d_supported(int dtype, int Cin, int Cout, int ks);
+int hrnet_conv3d(int dtype, const void* x, const void* w_packed, const float* scale, const float* shift,
+                 const void* res, void* y, int N, int D, int H, int W, int Cin, int Cout, int ks, int relu,
+                 hr_stream_t stream);
+int hrnet_pack_weights3d(int dtype, const float* w, void* out, int Cout, int Cin, int ks, int Cout_pad, int Cin_pad,
+                         int transposed, hr_stream_t stream);
+int hrnet_maxpool3d(int dtype, const void* x, void* y, int N, int D, int H, int W, int C, hr_stream_t stream);
+int hrnet_deconv3d_k2s2(int dtype, const void* x, const void* w_packed, const float* scale, const float* shift,
+                        const void* add, void* y, int N, int D, int H, int W, int Cin, int Cout, int relu,
+                        hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
