@@ -882,6 +882,73 @@ int hrnet_deconv3d_k2s2(int dtype, const void* x, const void* w_packed, const fl
                         hr_stream_t stream);
 
 /*
+ * V2V training (csrc/conv3d_train.hip): what a training step of V2V needs beside the entries above. Same layout and
+ * rules: NDHWC f32, 64-bit element offsets, Cin % 4 == 0, Cout % 16 == 0, pad channels zero on the way in and kept zero
+ * on the way out, f32 only. Stream-ordered, no allocation, no host synchronisation, NO atomics: every sum has one
+ * fixed order (per-workgroup or per-split partials in caller scratch, added in index order by a second launch), so a
+ * call is bit-reproducible. Every argument check comes before the first launch. rows = N * D * H * W throughout.
+ * The raw convolution output z of a training layer is hrnet_conv3d with scale = NULL, shift = bias, no res, no ReLU.
+ *
+ * bn3d_parts: the number P of partial rows the BatchNorm entries use for `rows` rows (at most 256); 0 for rows < 1.
+ * bn3d_stats: training-mode BatchNorm3d statistics of z [rows][C]: mean, biased variance -> invstd = 1/sqrt(var + eps),
+ *   scale = gamma * invstd, shift = beta - mean * scale (gamma / beta NULL = 1 / 0), all [C]. Two passes, sum z and then
+ *   sum (z - mean)^2, never E[z^2] - E[z]^2. running_mean / running_var (both or neither; the first Creal channels)
+ *   are updated with `momentum`, the variance unbiased (rows / (rows - 1)); *num_batches_tracked += 1 if not NULL.
+ *   rows >= 2 (HR_E_BADARG with torch's "Expected more than 1 value per channel when training" otherwise);
+ *   C <= 1024. scratch: 2 * P * C floats.
+ * bn3d_apply: y = z * scale + shift (one fmaf); other_after_relu == 0: + other, then ReLU if relu (Res3DBlock);
+ *   other_after_relu != 0: ReLU if relu, then + other (the decoder's upsample + skip). other may be NULL.
+ * bn3d_bwd: with g = dy where the forward's ReLU passed (mask_y != NULL: where the saved output mask_y > 0;
+ *   recompute_mask != 0: where fmaf(z, scale, shift) > 0, for a layer that added something AFTER its ReLU; neither: no
+ *   ReLU) and xhat = (z - mean) * invstd:  dz = scale * (g - mean(g) - xhat * mean(g * xhat)),  dgamma = sum g * xhat,
+ *   dbeta = sum g,  dbias (the convolution's, under the BatchNorm) = 0: sum dz is scale * (sum g - rows * mean(g) -
+ *   mean(g xhat) * sum xhat), whose first two terms cancel and whose sum xhat is zero by the definition of the batch
+ *   mean. dother (NULL or [rows][C]) receives g, written or with accumulate_other added to: the gradient of a residual
+ *   input. (The gradient of a tensor added after the ReLU is dy itself: no pass.) dgamma / dbeta / dbias: NULL = skip,
+ *   the first Creal channels, added to with accumulate_params. z == NULL (a layer without BatchNorm): only
+ *   dbias (+)= sum dy is formed; dz, dother, mask_y, dgamma, dbeta must be NULL. scratch: (2 * P + 2) * C floats.
+ * maxpool3d_bwd: x [N,D,H,W,C] is the pool's saved input, dy [N,D/2,H/2,W/2,C]; dx gets dy at the FIRST maximum of each
+ *   2x2x2 window in (d, h, w) scan order (strict >: an all-equal window sends it to element 0, as torch on the CPU) and
+ *   zero elsewhere; with accumulate it is added to dx.
+ * pack_weights3d_dgrad: Conv3d's OIDHW to [ks^3][Cin_pad][Cout_pad] with out[tap][ci][co] = w[co][ci][ks^3 - 1 - tap]:
+ *   transposed and tap-reversed, so that hrnet_conv3d(dz, out, NULL, zeros, res, dx, ..., Cin := Cout_pad,
+ *   Cout := Cin_pad, ks, 0) is the input gradient (+ res). Cin_pad is the output side there: a multiple of 16 (the
+ *   first layer's 4 input channels come out as 16, of which the layout transpose keeps the real ones).
+ * deconv3d_k2s2_dgrad: dx[n,d,h,w,ci] (+)= sum over (a,b,c), co of w[ci][co][a][b][c] * dz[n,2d+a,2h+b,2w+c,co];
+ *   w_packed [8][Cin][Cout] = pack_weights3d(w, Cout := Cin, Cin := Cout, ks 2, transposed 0). N, D, H, W are dx's.
+ * conv3d_wgrad_scratch: pure host query: *bytes of scratch and *nsplit voxel splits that conv3d_wgrad uses for this
+ *   shape (N, D, H, W: the volume the kernel walks - the convolution's, or the deconvolution's INPUT volume), and, if
+ *   split_voxels != NULL, the voxels of one split: split k owns voxels [k * split_voxels, (k + 1) * split_voxels),
+ *   the last one what is left.
+ * conv3d_wgrad: dw[co][ci][tap] (+)= sum_v dz[v,co] * x[v + tap,ci] (taps outside the volume contribute nothing), OIDHW
+ *   [Cout_real][Cin_real][ks^3]; deconv != 0: dw[ci][co][tap] (+)= sum_v x[v,ci] * dz[2v + tap,co], IODHW, ks = 2,
+ *   x [N,D,H,W,Cin], dz [N,2D,2H,2W,Cout]. The voxels are split over workgroups into nsplit partial sums in scratch,
+ *   which a second launch adds in split order. accumulate != 0 adds to dw, else dw is overwritten.
+ */
+int hrnet_bn3d_parts(long long rows);
+int hrnet_bn3d_stats(int dtype, const void* z, const float* gamma, const float* beta, float* scratch, float* mean,
+                     float* invstd, float* scale, float* shift, float* running_mean, float* running_var,
+                     long long* num_batches_tracked, int N, int D, int H, int W, int C, int Creal, float momentum,
+                     float eps, hr_stream_t stream);
+int hrnet_bn3d_apply(int dtype, const void* z, const float* scale, const float* shift, const void* other, void* y, int N,
+                     int D, int H, int W, int C, int relu, int other_after_relu, hr_stream_t stream);
+int hrnet_bn3d_bwd(int dtype, const void* dy, const void* z, const void* mask_y, const float* scale, const float* shift,
+                   const float* mean, const float* invstd, float* scratch, void* dz, void* dother, float* dgamma,
+                   float* dbeta, float* dbias, int N, int D, int H, int W, int C, int Creal, int recompute_mask,
+                   int accumulate_other, int accumulate_params, hr_stream_t stream);
+int hrnet_maxpool3d_bwd(int dtype, const void* x, const void* dy, void* dx, int N, int D, int H, int W, int C,
+                        int accumulate, hr_stream_t stream);
+int hrnet_pack_weights3d_dgrad(int dtype, const float* w, void* out, int Cout, int Cin, int ks, int Cout_pad,
+                               int Cin_pad, hr_stream_t stream);
+int hrnet_deconv3d_k2s2_dgrad(int dtype, const void* dz, const void* w_packed, void* dx, int N, int D, int H, int W,
+                              int Cin, int Cout, int accumulate, hr_stream_t stream);
+int hrnet_conv3d_wgrad_scratch(int dtype, int N, int D, int H, int W, int Cin, int Cout, int ks, int deconv,
+                               long long* bytes, int* nsplit, long long* split_voxels);
+int hrnet_conv3d_wgrad(int dtype, const void* x, const void* dz, void* scratch, long long scratch_bytes, float* dw, int N,
+                       int D, int H, int W, int Cin, int Cout, int Cin_real, int Cout_real, int ks, int deconv,
+                       int accumulate, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
