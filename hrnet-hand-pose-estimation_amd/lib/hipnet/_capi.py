@@ -164,6 +164,10 @@ _SIGS = {
     'hrnet_deconv3d_k2s2_dgrad': [_c_int] + [_c_vp] * 3 + [_c_int] * 7 + [_c_vp],
     'hrnet_conv3d_wgrad_scratch': [_c_int] * 9 + [ctypes.POINTER(_c_i64), _ip, ctypes.POINTER(_c_i64)],
     'hrnet_conv3d_wgrad': [_c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp] + [_c_int] * 11 + [_c_vp],
+    'hrnet_pointwise_nchw_supported': [_c_int] * 3,
+    'hrnet_pointwise_nchw': [_c_int] + [_c_vp] * 4 + [_c_int] * 3 + [_c_i64, _c_vp],
+    'hrnet_pointwise_nchw_parts': [_c_int, _c_i64],
+    'hrnet_pointwise_nchw_bwd': [_c_int] + [_c_vp] * 7 + [_c_i64] + [_c_int] * 3 + [_c_i64, _c_vp],
     'hrnet_joints_loss_fwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints3d_loss_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],
@@ -181,7 +185,8 @@ _SIGS = {
 _PLAIN = {'hrnet_abi_version', 'hrnet_ew_table_blocks', 'hrnet_conv_rows_bwdstats', 'hrnet_conv_route', 'hrnet_conv_ring_sum_enable', 'hrnet_conv_ring_enable', 'hrnet_conv_ring_supported', 'hrnet_conv_tiles', 'hrnet_conv_tile_walk', 'hrnet_conv_tiles_bwdstats', 'hrnet_wgrad_splits', 'hrnet_wgrad_tiles', 'hrnet_wgrad_blocks_per_split', 'hrnet_bwd_fused_supported', 'hrnet_bwd_fused_splits', 'hrnet_bwd_fused_kernel_name', 'hrnet_reduce_blocks',
           'hrnet_pack_blocks', 'hrnet_bwd_pw_supported', 'hrnet_bwd_pw_rows_supported', 'hrnet_bwd_pw_splits', 'hrnet_bwd_pw_kernel_name',
           'hrnet_conv_kernel_name', 'hrnet_wgrad_kernel_name', 'hrnet_conv_mode', 'hrnet_deform_conv_wgrad_blocks',
-          'hrnet_head_mix_rows', 'hrnet_head_mix_supported', 'hrnet_conv3d_supported', 'hrnet_bn3d_parts'}
+          'hrnet_head_mix_rows', 'hrnet_head_mix_supported', 'hrnet_conv3d_supported', 'hrnet_bn3d_parts',
+          'hrnet_pointwise_nchw_supported', 'hrnet_pointwise_nchw_parts'}
 EXPORTED = sorted(list(_SIGS) + ['hrnet_last_error_string', 'hrnet_event_create'])
 
 _lib = None

@@ -89,7 +89,12 @@ class HipNet(object):
     def _records(self):
         self.convs, self.bns, self.bn_list, self.bias_pad = {}, {}, {}, {}
         self.bn_list = []
+        # children the engine does not run (pose_hrnet_volumetric's confidence head): they keep their parameters in the
+        # flat buffers like every other, but nothing of theirs is packed or recorded
+        skip = tuple(getattr(self.module, 'hip_skip_prefixes', ()))
         for name, m in self.module.named_modules():
+            if skip and name.startswith(skip):
+                continue
             if isinstance(m, nn.Conv2d):
                 r = ConvRec(name, m, stem=(name == 'conv1'))
                 es = torch.empty((), dtype=self.compute_dtype).element_size()

@@ -949,6 +949,27 @@ int hrnet_conv3d_wgrad(int dtype, const void* x, const void* dz, void* scratch, 
                        int accumulate, hr_stream_t stream);
 
 /*
+ * 1x1 convolution on NCHW f32 with the module's own weight, read in place (csrc/pointwise.hip): process_features of the
+ * volumetric model (reference lib/models/triangulation.py:345-349). f32 only; P = H * W pixels per plane.
+ *   forward:  y[n,o,p] = bias[o] + sum_c w[o,c] x[n,c,p]; x [N,Cin,P], w [Cout,Cin], bias [Cout] or NULL, y [N,Cout,P].
+ *   backward: dx[n,c,p] = sum_o w[o,c] dy[n,o,p], dw[o,c] = sum_{n,p} dy[n,o,p] x[n,c,p], db[o] = sum_{n,p} dy[n,o,p];
+ *             each of dx, dw, db may be NULL (not all three) and the others do not depend on which are. dw and db go
+ *             through `scratch`: hrnet_pointwise_nchw_parts(N, P) rows of Cout * Cin + Cout floats, one per workgroup
+ *             of the first launch, added in index order by a second one. scratch is needed only with dw or db.
+ * hrnet_pointwise_nchw_supported: 1 for f32, 1 <= Cin <= 65536, 1 <= Cout <= 64. Further limits, refused: N <= 65535,
+ * P <= 2^30, N * P * max(Cin, Cout) <= 2^40. hrnet_pointwise_nchw_parts: 0 for sizes outside these limits.
+ * No atomics: a call is bit-reproducible. Any P, Cin and Cout within the limits; 16-byte accesses are used when
+ * P % 4 == 0 (Cin % 4 == 0 for w) and the pointers are 16-byte aligned.
+ */
+int hrnet_pointwise_nchw_supported(int dtype, int Cin, int Cout);
+int hrnet_pointwise_nchw(int dtype, const float* x, const float* w, const float* bias, float* y, int N, int Cin,
+                         int Cout, long long P, hr_stream_t stream);
+int hrnet_pointwise_nchw_parts(int N, long long P);
+int hrnet_pointwise_nchw_bwd(int dtype, const float* x, const float* w, const float* dy, float* dx, float* dw, float* db,
+                             float* scratch, long long scratch_floats, int N, int Cin, int Cout, long long P,
+                             hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
