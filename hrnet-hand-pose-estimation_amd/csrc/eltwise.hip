@@ -1533,8 +1533,9 @@ int hr_launch_bn_bwd_finalize(const HrOp& op, hipStream_t s) {
 // Transpose of a bilinear upsampling over ALL channels (the head without its concat, gemm_pw.hip): g[n][h][w][c] =
 // sum over the H x W pixels (Y, X) whose bilinear footprint touches (h, w) of weight * G[n][Y][X][c]. Separable and
 // streamed: a thread owns one low-resolution column w and one 16-byte channel vector, walks the full-resolution
-// rows Y of its workgroup's band in order, forms the row's x-contraction (the <= 2*scale+1 pixels whose x taps hit w;
-// weights evaluated once per thread) and adds it into the two low-resolution rows Y touches, which live in
+// rows Y of its workgroup's band in order, forms the row's x-contraction (the pixels whose x taps hit w: at most
+// 2*scale+1 with align_corners = 0; the weights of the first CATB_MAXW columns of the window are evaluated once per
+// thread, those of a wider align_corners window per row) and adds it into the two low-resolution rows Y touches, which live in
 // registers and are stored as the walk leaves them. Every element of G is read once per band it belongs to (bands
 // overlap by the footprint of their border rows), with unit-stride 16-byte loads across the channel vectors.
 struct UpTArgs {
@@ -1559,7 +1560,7 @@ __global__ __launch_bounds__(256) void upsample_t_kernel(UpTArgs a) {
   const int w = (int)threadIdx.x / a.cvw;
   if (w >= a.ws || cv >= cvtot) return;
   const int h_lo = band * a.rband, h_hi = min(a.hs, h_lo + a.rband);
-  // x window of column w and its weights (zero entries are skipped in the walk)
+  // x window of column w and the weights of its first CATB_MAXW columns (zero entries are skipped in the walk)
   int dx0, dx1;
   bilin_window(w, a.ws, a.W, a.align, dx0, dx1);
   float wxs[CATB_MAXW];
@@ -1605,6 +1606,20 @@ __global__ __launch_bounds__(256) void upsample_t_kernel(UpTArgs a) {
         v16_unpack<T>(*(const V16*)(row + (size_t)j * a.C * sizeof(T)), gv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) r[k] = fmaf(wxs[j], gv[k], r[k]);
+      }
+    }
+    // the rest of a window wider than CATB_MAXW (align_corners with few source columns: 24 columns for 3 -> 24),
+    // in the same ascending order with the weights re-evaluated per row; no turn of this loop for any other shape
+    for (int dx = dx0 + CATB_MAXW; dx < dx1; ++dx) {
+      int x0, x1;
+      float lx;
+      bilin_src(dx, a.ws, a.W, a.align, x0, x1, lx);
+      const float wx = (x0 == w ? 1.f - lx : 0.f) + (x1 == w ? lx : 0.f);
+      if (wx != 0.f) {
+        float gv[VEC];
+        v16_unpack<T>(*(const V16*)(gbase + ((size_t)Y * a.W + dx) * a.C * sizeof(T)), gv);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) r[k] = fmaf(wx, gv[k], r[k]);
       }
     }
     const float wa = y1 != y0 ? 1.f - ly : 1.f, wb = y1 != y0 ? ly : 0.f;
@@ -1660,6 +1675,12 @@ int hr_launch_upsample_t(const HrOp& op, hipStream_t s) {
     ws[k] = op.i[HR_UPSAMPLE_T_I_OUT_W1 + 2 * k];
     HR_REQUIRE(outs[k] && hs[k] >= 1 && ws[k] >= 1 && hs[k] <= H && ws[k] <= W && ws[k] <= 256,
                "upsample_t: output %d: %dx%d from %dx%d", k, hs[k], ws[k], H, W);
+    // ceil(W / ws) <= 8. What this guarantees: with align_corners = 0 every non-zero x weight of a column lies in
+    // the first CATB_MAXW entries of its window (the registers of upsample_t_kernel), and with align_corners = 1
+    // the window is at most 2 (W - 1) / (ws - 1) + 5 <= 2 * CATB_MAXW columns, whose rest the kernel walks after the
+    // registers. The kernel is correct for any window; the gate bounds its work per row, not its reach. Checked for
+    // every output before the first launch, so a refused call writes nothing.
+    HR_REQUIRE(2 * ((W + ws[k] - 1) / ws[k]) + 4 <= CATB_MAXW, "upsample_t: scale %d x %d too large", W, ws[k]);
   }
   // integer scales 2 / 4 / 8 (the head): all outputs from ONE pass over G (head_mix.hip)
   if (op.i[HR_UPSAMPLE_T_I_STREAMED] == 0 && hr_upsample_t_tile(dtype, op.p[HR_UPSAMPLE_T_P_G], outs, hs, ws, nout, N,
@@ -1669,7 +1690,6 @@ int hr_launch_upsample_t(const HrOp& op, hipStream_t s) {
     UpTArgs a;
     a.g = (const char*)op.p[HR_UPSAMPLE_T_P_G]; a.out = (char*)outs[k];
     a.N = N; a.H = H; a.W = W; a.C = Cc; a.hs = hs[k]; a.ws = ws[k]; a.align = align;
-    HR_REQUIRE(2 * ((a.W + a.ws - 1) / a.ws) + 4 <= CATB_MAXW, "upsample_t: scale %d x %d too large", a.W, a.ws);
     const int cvtot = a.C / vec;
     a.cvw = 256 / a.ws;
     if (a.cvw > cvtot) a.cvw = cvtot;
