@@ -168,7 +168,10 @@ _SIGS = {
     'hrnet_pointwise_nchw': [_c_int] + [_c_vp] * 4 + [_c_int] * 3 + [_c_i64, _c_vp],
     'hrnet_pointwise_nchw_parts': [_c_int, _c_i64],
     'hrnet_pointwise_nchw_bwd': [_c_int] + [_c_vp] * 7 + [_c_i64] + [_c_int] * 3 + [_c_i64, _c_vp],
-    'hrnet_joints_loss_fwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
+    'hrnet_view_fusion_supported': [_c_int] * 3,
+    'hrnet_view_fusion': [_c_int, _c_vp, _pp, _c_vp] + [_c_int] * 4 + [_c_float] * 2 + [_c_vp],
+    'hrnet_view_fusion_bwd': [_c_int, _c_vp, _pp, _c_vp, _c_vp, _pp] + [_c_int] * 4 + [_c_float] * 2 + [_c_vp],
+    'hrnet_joints_loss_fwd':[_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints3d_loss_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints3d_loss_bwd': [_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
@@ -186,7 +189,7 @@ _PLAIN = {'hrnet_abi_version', 'hrnet_ew_table_blocks', 'hrnet_conv_rows_bwdstat
           'hrnet_pack_blocks', 'hrnet_bwd_pw_supported', 'hrnet_bwd_pw_rows_supported', 'hrnet_bwd_pw_splits', 'hrnet_bwd_pw_kernel_name',
           'hrnet_conv_kernel_name', 'hrnet_wgrad_kernel_name', 'hrnet_conv_mode', 'hrnet_deform_conv_wgrad_blocks',
           'hrnet_head_mix_rows', 'hrnet_head_mix_supported', 'hrnet_conv3d_supported', 'hrnet_bn3d_parts',
-          'hrnet_pointwise_nchw_supported', 'hrnet_pointwise_nchw_parts'}
+          'hrnet_pointwise_nchw_supported', 'hrnet_pointwise_nchw_parts', 'hrnet_view_fusion_supported'}
 EXPORTED = sorted(list(_SIGS) + ['hrnet_last_error_string', 'hrnet_event_create'])
 
 _lib = None

@@ -3,7 +3,7 @@
     python tools/evaluate_3D.py --cfg <yaml> --model_path <state_dict.pth.tar> --views '[1,2,3,4]' --batch_size 32
         [--triangulation {dlt,ransac}] [--ransac_epsilon 25] [--ransac_iters 0] [--seed 0]
 
-cfg -> MODEL.NAME pose_hrnet / pose_hrnet_softmax, strict load ('module.' prefix stripped) -> the multi-view reader
+cfg -> MODEL.NAME pose_hrnet / pose_hrnet_softmax / multiview_pose_hrnet, strict load ('module.' prefix stripped) -> the multi-view reader
 MHP_mv (dataset/mhp.py) on DATASET.TEST_SET of <DATA_DIR>/MHP, whatever DATASET.TEST_DATASET names (every 2-D MHP
 yaml names a single-view reader, on which the reference's tool fails); a missing <DATA_DIR>/MHP/annotated_frames is an
 error, there is no synthetic multi-view loader. Per batch of B frames and V views, on the device: model(imgs) ->
@@ -13,6 +13,10 @@ every joint of every frame -> core/evaluate3d.py accumulators (vectorised, no pe
 fps (multi-view frames per second of model + decode + triangulation, after warm-up as tools/evaluate_2D.py), the
 2-D and 3-D EPE and both PCK AUCs (the reference's trapezoid, :121,134); writes mse2d_each_joint.txt,
 mse3d_each_joint.txt, PCK2d.txt and PCK3d.txt to <OUTPUT_DIR>/eval3D_results_<EXP_NAME>/.
+
+MODEL.NAME multiview_pose_hrnet (models/multiview_pose_hrnet.py, trained by tools/train_fusion.py) takes the batch as
+(B, V, 3, H, W); its FUSED heat maps are decoded and triangulated, or its single-view maps when MODEL.AGGRE is false. The
+lifting, DLT or --triangulation ransac, is the same.
 
 The reference lifts pose_hrnet predictions with DLT_sii_pytorch (lib/utils/misc.py:64-97), two shifted inverse
 iterations from a torch.rand start; this tool computes the vector they converge to (see utils/multiview.py).
@@ -54,12 +58,13 @@ from config import cfg, update_config
 from core.evaluate2d import load_checkpoint_state
 from core.evaluate3d import Eval3DAccumulator, auc
 from dataset import mhp
-from models import pose_hrnet, pose_hrnet_softmax
+from models import multiview_pose_hrnet, pose_hrnet, pose_hrnet_softmax
 from utils.heatmap_decoding import get_final_preds
 from utils.multiview import (MAX_HYPOTHESES, all_view_pairs, sample_view_pairs, triangulate_batch_of_points,
                              triangulate_ransac_batch)
 
-MODELS = {'pose_hrnet': pose_hrnet.get_pose_net, 'pose_hrnet_softmax': pose_hrnet_softmax.get_pose_net}
+MODELS = {'pose_hrnet': pose_hrnet.get_pose_net, 'pose_hrnet_softmax': pose_hrnet_softmax.get_pose_net,
+          'multiview_pose_hrnet': multiview_pose_hrnet.get_pose_net}
 NOT_BUILT = ('alg', 'ransac', 'vol', 'vol_CPM', 'FTL')
 
 
@@ -112,6 +117,14 @@ def build_model(name):
     return MODELS[name]
 
 
+def heatmaps_of(model, imgs, V, config):
+    """the heat maps to decode, (B * V, K, h, w) in slot order b * V + v, of a batch of images in that order"""
+    if config.MODEL.NAME == 'multiview_pose_hrnet':
+        out = model(imgs.cuda(non_blocking=True).view(imgs.shape[0] // V, V, *imgs.shape[1:]))
+        return out[0] if config.MODEL.AGGRE else out          # (fused, single), or single alone
+    return model(imgs)[0]                                     # (heatmaps, inter_feat[, temperature])
+
+
 def check_lifting(args, config):
     """--triangulation against the cfg: the reference's DIRECT_OPTIMIZATION refinement is not built"""
     if args.triangulation == 'ransac' and config.MODEL.DIRECT_OPTIMIZATION:
@@ -159,7 +172,7 @@ def main(argv=None):
                 pairs = sample_view_pairs(B * K, V, args.ransac_iters, rng).to(device)
             torch.cuda.synchronize()
             t0 = time.time()
-            hm = model(imgs)[0]      # (heatmaps, inter_feat[, temperature])
+            hm = heatmaps_of(model, imgs, V, cfg)
             pred = get_final_preds(hm, cfg.MODEL.HEATMAP_SOFTMAX)     # (B*V, K, 2) heat-map pixels
             proj = intrinsic[:, None] @ extrinsic                      # (B, V, 3, 4)
             if ransac:

@@ -970,6 +970,27 @@ int hrnet_pointwise_nchw_bwd(int dtype, const float* x, const float* w, const fl
                              hr_stream_t stream);
 
 /*
+ * Cross-view heat-map fusion of multiview_pose_hrnet (csrc/view_fusion.hip; reference
+ * lib/models/multiview_pose_hrnet.py:57-71). H, F, dF, dH are [B][V][K][P] f32 (P = h * w); W and dW are HOST arrays of
+ * V * (V - 1) device pointers, the way hrnet_sum_terms takes its sources; W[n] is the [P_out][P_in] weight of an
+ * nn.Linear, read in place (nothing is packed or copied). n(i,j) = i * (V - 1) + (rank of j among the views != i).
+ *   forward:  F[b,i,k,:] = w_self * H[b,i,k,:] + w_other * sum_{j != i} H[b,j,k,:] @ W[n(i,j)]^T        (one launch)
+ *   backward: dH[b,j,k,:] = w_self * dF[b,j,k,:] + w_other * sum_{i != j} dF[b,i,k,:] @ W[n(i,j)]       (one launch)
+ *             dW[n(i,j)] = w_other * dF[:,i]^T @ H[:,j], summed over the B * K rows                      (one launch)
+ *             dH may be NULL (then W may be NULL too); dW may be NULL (then H may be NULL), and a NULL entry of dW
+ *             skips that matrix. Not both NULL. Neither half needs scratch memory.
+ * hrnet_view_fusion_supported: 1 for f32, 2 <= V <= 4, 1 <= P <= 2^20. Further limits, refused: B, K >= 1,
+ * B * V * K * P < 2^31. No atomics: every sum has one fixed order, so a call is bit-reproducible. 16-byte accesses are
+ * used when P % 4 == 0 and every pointer is 16-byte aligned; any other P takes element-wise loads in the same kernels.
+ * A weight element is read once per forward and once per dH pass while B * K <= 192; each dW element is written once.
+ */
+int hrnet_view_fusion_supported(int dtype, int V, int P);
+int hrnet_view_fusion(int dtype, const float* H, const void* const* W, float* F, int B, int V, int K, int P,
+                      float w_self, float w_other, hr_stream_t stream);
+int hrnet_view_fusion_bwd(int dtype, const float* H, const void* const* W, const float* dF, float* dH, void* const* dW,
+                          int B, int V, int K, int P, float w_self, float w_other, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
