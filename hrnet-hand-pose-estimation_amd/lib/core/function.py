@@ -4,7 +4,8 @@ branch; validate :790-828; AverageMeter :1272-1378).
 
 Same call signatures, loss-dict keys, log line format and tensorboard scalar names; only the
 generic 2-D dataset branch (HandGraph_kpt / RHD_kpt / FreiHand_kpt / MHP_kpt ...) exists here -
-the multi-view / temporal / CPM branches belong to other model families.
+the multi-view / temporal / CPM branches belong to other model families. MODEL.NAME pose_hrnet_transformer on MHP_seq
+batches goes through `_poseformer_forward` in both loops.
 
 `validate` also accepts 'RHD' (the evaluation-set reader, dataset/rhd.py; tools/train.py serves it with heat
 maps). The reference's validate skips that name (function.py:800), so validating on the shipped RHD yaml's
@@ -116,8 +117,34 @@ def _to_device(t, device):
     return t.cuda(device, non_blocking=True) if device is not None else t.cuda(non_blocking=True)
 
 
+def _poseformer_forward(config, imgs, model):
+    """pose_hrnet_transformer on an MHP_seq batch (reference function.py:55-66 training, :665 validation): `imgs` is
+    the loader's frame-major window batch (F * S, 3, H, W), slot f * S + s with s = b * 4 + view (dataset/mhp.py). The
+    refined pose (S, K, 2) of the centre frame is pose2d_pred; the batch's ground truth and visibility are already the
+    centre frame's four views in the same order s. Deviation: with WITH_HEATMAP_LOSS the reference passes all S * F
+    predicted maps against S targets (:62-66 with computeLosses), which cannot run; here the CENTRE frame's maps are
+    compared."""
+    seq = [int(s) for s in config.DATASET.SEQ_IDX]
+    F = len(seq)
+    outputs = model(imgs, frames=F)
+    centre = seq.index(0) if 0 in seq else F // 2
+    heatmaps = outputs[1]
+    S = heatmaps.shape[0] // F
+    return heatmaps[centre * S:(centre + 1) * S], outputs[0]
+
+
 def _forward_and_losses(config, ret, model, recorder, device):
     imgs, heatmaps_gt, pose2d_gt, visibility = ret['imgs'], ret['heatmaps'], ret['pose2d'], ret['visibility']
+    if config.MODEL.NAME == 'pose_hrnet_transformer':
+        heatmaps_pred, pose2d_pred = _poseformer_forward(config, _to_device(imgs, device), model)
+        if config.LOSS.WITH_HEATMAP_LOSS:
+            heatmaps_gt = _to_device(heatmaps_gt, device)
+        if config.LOSS.WITH_POSE2D_LOSS or config.LOSS.WITH_BONE_LOSS:
+            pose2d_gt = _to_device(pose2d_gt, device)
+        if config.LOSS.WITH_POSE2D_LOSS:
+            visibility = _to_device(visibility, device)
+        visibility = visibility.reshape(visibility.shape[0], -1)
+        return imgs, recorder.computeLosses(heatmaps_pred, heatmaps_gt, pose2d_pred, pose2d_gt, visibility=visibility)
     # pose_hrnet returns (heatmaps, inter_feat); pose_hrnet_softmax adds the temperature as a third item
     # (the reference's 2-tuple unpack at lib/core/function.py:68 cannot take that model; SURVEY 8f-1)
     outputs = model(_to_device(imgs, device))

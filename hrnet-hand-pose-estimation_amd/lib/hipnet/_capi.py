@@ -171,6 +171,17 @@ _SIGS = {
     'hrnet_view_fusion_supported': [_c_int] * 3,
     'hrnet_view_fusion': [_c_int, _c_vp, _pp, _c_vp] + [_c_int] * 4 + [_c_float] * 2 + [_c_vp],
     'hrnet_view_fusion_bwd': [_c_int, _c_vp, _pp, _c_vp, _c_vp, _pp] + [_c_int] * 4 + [_c_float] * 2 + [_c_vp],
+    'hrnet_tf_supported': [_c_int] * 3,
+    'hrnet_tf_layernorm_scratch': [_c_i64, _c_int],
+    'hrnet_tf_layernorm': [_c_vp] * 4 + [_c_i64, _c_int, _c_float, _c_vp],
+    'hrnet_tf_layernorm_bwd': [_c_vp] * 7 + [_c_i64, _c_i64, _c_int, _c_float, _c_vp],
+    'hrnet_tf_linear': [_c_vp] * 7 + [_c_i64] + [_c_int] * 3 + [_c_vp],
+    'hrnet_tf_linear_bwd': [_c_vp] * 8 + [_c_i64] + [_c_int] * 3 + [_c_vp],
+    'hrnet_tf_attention': [_c_vp] * 2 + [_c_int] * 4 + [_c_float, _c_vp],
+    'hrnet_tf_attention_bwd': [_c_vp] * 3 + [_c_int] * 4 + [_c_float, _c_vp],
+    'hrnet_tf_frame_mean': [_c_vp] * 4 + [_c_i64, _c_int, _c_i64, _c_vp],
+    'hrnet_tf_frame_mean_bwd': [_c_vp] * 6 + [_c_i64, _c_int, _c_i64, _c_vp],
+    'hrnet_tf_add_rows': [_c_vp] * 3 + [_c_i64, _c_int, _c_int, _c_vp],
     'hrnet_joints_loss_fwd':[_c_vp] * 4 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints_loss_bwd': [_c_vp] * 5 + [_c_int] * 2 + [_c_vp],
     'hrnet_joints3d_loss_fwd': [_c_vp] * 3 + [_c_int] * 2 + [_c_vp],
@@ -189,7 +200,9 @@ _PLAIN = {'hrnet_abi_version', 'hrnet_ew_table_blocks', 'hrnet_conv_rows_bwdstat
           'hrnet_pack_blocks', 'hrnet_bwd_pw_supported', 'hrnet_bwd_pw_rows_supported', 'hrnet_bwd_pw_splits', 'hrnet_bwd_pw_kernel_name',
           'hrnet_conv_kernel_name', 'hrnet_wgrad_kernel_name', 'hrnet_conv_mode', 'hrnet_deform_conv_wgrad_blocks',
           'hrnet_head_mix_rows', 'hrnet_head_mix_supported', 'hrnet_conv3d_supported', 'hrnet_bn3d_parts',
-          'hrnet_pointwise_nchw_supported', 'hrnet_pointwise_nchw_parts', 'hrnet_view_fusion_supported'}
+          'hrnet_pointwise_nchw_supported', 'hrnet_pointwise_nchw_parts', 'hrnet_view_fusion_supported',
+          'hrnet_tf_supported', 'hrnet_tf_layernorm_scratch'}
+_RET64 = {'hrnet_tf_layernorm_scratch'}      # plain helpers that return long long
 EXPORTED = sorted(list(_SIGS) + ['hrnet_last_error_string', 'hrnet_event_create'])
 
 _lib = None
@@ -211,7 +224,7 @@ def lib():
         for name, args in _SIGS.items():
             fn = getattr(l, name)
             fn.argtypes = args
-            fn.restype = ctypes.c_int
+            fn.restype = ctypes.c_int64 if name in _RET64 else ctypes.c_int
         l.hrnet_last_error_string.argtypes = []
         l.hrnet_last_error_string.restype = ctypes.c_char_p
         l.hrnet_event_create.argtypes = []

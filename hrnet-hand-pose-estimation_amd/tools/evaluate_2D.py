@@ -11,7 +11,8 @@ annotations exist, otherwise the synthetic RHD-shaped loader (24 batches unless 
 coordinates are rescaled to original-image pixels with `* crop_size / hm_size + corner` (:235-240). The MHP readers
 (dataset/mhp.py: MHP, MHP_kpt, MHP_seq) serve <DATA_DIR>/MHP; their batches carry `hm_inverse`, the inverse of each
 sample's heat-map matrix, and the coordinates are mapped back through it. The reference scales MHP by 640/64 and
-480/64 instead (:241-245), which does not invert its own 'short'-scale crop of the frame.
+480/64 instead (:241-245), which does not invert its own 'short'-scale crop of the frame. With MODEL.NAME
+pose_hrnet_transformer on MHP_seq the poses evaluated are the model's refined poses of the centre frames.
 """
 import argparse
 import os
@@ -24,7 +25,7 @@ import torch
 from config import cfg, update_config
 from core.evaluate2d import Eval2DAccumulator, load_checkpoint_state
 from dataset.build import make_dataloader
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax  # noqa: F401
+from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax, pose_hrnet_transformer  # noqa: F401
 from utils.heatmap_decoding import get_final_preds
 
 
@@ -70,8 +71,12 @@ def main():
             imgs = ret['imgs'].to(device)
             torch.cuda.synchronize()
             t0 = time.time()
-            hm = model(imgs)[0]      # (heatmaps, inter_feat[, temperature])
-            pred = get_final_preds(hm, cfg.MODEL.HEATMAP_SOFTMAX)
+            if cfg.MODEL.NAME == 'pose_hrnet_transformer':
+                # MHP_seq's frame-major window batch -> the refined poses of the centre frames, (4 B, K, 2)
+                pred = model(imgs, frames=len(cfg.DATASET.SEQ_IDX))[0]
+            else:
+                hm = model(imgs)[0]      # (heatmaps, inter_feat[, temperature])
+                pred = get_final_preds(hm, cfg.MODEL.HEATMAP_SOFTMAX)
             torch.cuda.synchronize()
             if i >= 20 or i >= len(loader) // 2:
                 t_total += time.time() - t0

@@ -9,7 +9,7 @@ final_state.pth.tar (tools/train.py:126-405). One process per GPU; multi-GPU = R
 flat gradient overlapped with backward (hipnet.optim.GradSync), not DataParallel. Data: the RHD
 reader (dataset/rhd.py) when <DATA_DIR>/RHD/<subset>/anno_<subset>.pickle exists - DATASET.DATASET with TRAIN_SET
 for training (shuffled, this rank's share), TEST_DATASET with TEST_SET for validation (every sample, with heat
-maps) - or the MHP readers (dataset/mhp.py: MHP_kpt, MHP, and MHP_seq for pose_hrnet_PoseAggr) when
+maps) - or the MHP readers (dataset/mhp.py: MHP_kpt, MHP, and MHP_seq for pose_hrnet_PoseAggr and pose_hrnet_transformer, the latter on one GPU) when
 <DATA_DIR>/MHP/annotated_frames exists - otherwise the synthetic RHD-shaped loader (dataset/build.py). --batches-per-epoch caps a real epoch only
 when given; the synthetic loader is 8 batches (validation 2) unless it is given.
 """
@@ -24,7 +24,7 @@ from config import cfg, update_config
 from core.function import train, validate
 from core.loss import BoneLengthLoss, HeatmapLoss, JointAngleLoss, JointsMSELoss
 from dataset.build import make_dataloader
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax  # noqa: F401  (dispatched by name below)
+from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax, pose_hrnet_transformer  # noqa: F401  (dispatched by name below)
 from utils.utils import create_logger, get_optimizer, save_checkpoint
 
 
@@ -67,6 +67,11 @@ def main():
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
     torch.cuda.set_device(local)
     device = torch.device('cuda', local)
+    if world > 1 and cfg.MODEL.NAME == 'pose_hrnet_transformer':
+        # the gradient exchange (hipnet.optim.GradSync) covers the backbone's flat gradient buffer, not the autograd
+        # .grad tensors of the transformer head
+        raise ValueError('WORLD_SIZE {}: data-parallel training of pose_hrnet_transformer is not built; run one '
+                         'process'.format(world))
     if world > 1:
         torch.distributed.init_process_group(backend=cfg.DIST_BACKEND, device_id=device)
     master = rank == 0

@@ -991,6 +991,62 @@ int hrnet_view_fusion_bwd(int dtype, const float* H, const void* const* W, const
                           int B, int V, int K, int P, float w_self, float w_other, hr_stream_t stream);
 
 /*
+ * Transformer kernels of pose_hrnet_transformer, the reference's PoseFormer head (csrc/transformer.hip; reference
+ * lib/models/pose_hrnet_transformer.py:21-85, :195-221). Everything is f32, row-major (rows, C), 64-bit element
+ * offsets; an nn.Linear weight (Cout, Cin) is read in place. No float atomics: every sum has one fixed order, so a call
+ * is bit-reproducible. Every entry refuses what it has no kernel for (HR_E_BADARG) before it launches anything.
+ *
+ * The query, hrnet_tf_supported, takes (op, a, b): HR_TF_LAYERNORM (C, unused), HR_TF_LINEAR (Cin, Cout), both up to
+ * 65536; HR_TF_ATTENTION (N, hd): 1 <= N <= 64 tokens, 1 <= hd <= 128; HR_TF_FRAME_MEAN (F, unused): 1 <= F <= 65534.
+ * Rows: 1 .. 2^22.
+ *
+ * LayerNorm over the last axis: y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance. The backward recomputes
+ * the statistics from x and gives dx, dgamma, dbeta (each may be NULL, not all); the column sums are a two-stage
+ * reduction through `scratch`, at least the number of floats the scratch query returns for (rows, C), needed only with
+ * dgamma or dbeta.
+ *
+ * Linear: y = [res +] row_scale[row] * act(x W^T + bias). bias, res (rows, Cout), row_scale (rows) may be NULL. act:
+ * HR_TF_ACT_NONE or HR_TF_ACT_GELU (exact, the erf form). With GELU and `pre` not NULL the pre-activation x W^T + bias
+ * is stored there: the backward TAKES it as an input. Backward: g = dy * row_scale[row] * act'(pre);
+ * dx = g W, dW = g^T x, db = column sums of g; each may be NULL (not all), x may be NULL without dW, W without dx. The
+ * gradient of res is dy itself. Products run on mfma_f32_16x16x4f32; 16-byte accesses when Cin % 4 == 0, Cout % 4 == 0
+ * and the pointers are 16-byte aligned, element-wise loads in the same kernels otherwise (Cin = 2, Cout = 42).
+ *
+ * Attention on a packed qkv (S, N, 3, heads, hd): out (S, N, heads * hd) = softmax(q k^T * scale) v per (sequence,
+ * head), one wave each; scores and probabilities stay in LDS. The backward recomputes the probabilities from qkv and
+ * gives dqkv; nothing else is saved.
+ *
+ * Frame mean: y[s, :] = sum_f w[f] * x[s, f, :] + b[0] (b may be NULL), x (S, F, D). Backward: dx, dw (F), db (1), each
+ * may be NULL (not all).
+ *
+ * Add rows: y[r, :] = x[r, :] + pos[r % period, :], pos (period, C). Its backward is the identity for x
+ * and the frame mean with unit weights for pos.
+ */
+enum { HR_TF_LAYERNORM = 0, HR_TF_LINEAR = 1, HR_TF_ATTENTION = 2, HR_TF_FRAME_MEAN = 3 };
+enum { HR_TF_ACT_NONE = 0, HR_TF_ACT_GELU = 1 };
+int hrnet_tf_supported(int op, int a, int b);
+long long hrnet_tf_layernorm_scratch(long long rows, int C);
+int hrnet_tf_layernorm(const float* x, const float* gamma, const float* beta, float* y, long long rows, int C, float eps,
+                       hr_stream_t stream);
+int hrnet_tf_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta,
+                           float* scratch, long long scratch_floats, long long rows, int C, float eps,
+                           hr_stream_t stream);
+int hrnet_tf_linear(const float* x, const float* W, const float* bias, const float* res, const float* row_scale,
+                    float* y, float* pre, long long rows, int Cin, int Cout, int act, hr_stream_t stream);
+int hrnet_tf_linear_bwd(const float* x, const float* W, const float* dy, const float* pre, const float* row_scale,
+                        float* dx, float* dW, float* db, long long rows, int Cin, int Cout, int act,
+                        hr_stream_t stream);
+int hrnet_tf_attention(const float* qkv, float* out, int S, int N, int heads, int hd, float scale, hr_stream_t stream);
+int hrnet_tf_attention_bwd(const float* qkv, const float* dout, float* dqkv, int S, int N, int heads, int hd,
+                           float scale, hr_stream_t stream);
+int hrnet_tf_frame_mean(const float* x, const float* w, const float* b, float* y, long long S, int F, long long D,
+                        hr_stream_t stream);
+int hrnet_tf_frame_mean_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db,
+                            long long S, int F, long long D, hr_stream_t stream);
+int hrnet_tf_add_rows(const float* x, const float* pos, float* y, long long rows, int C, int period,
+                      hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
