@@ -33,6 +33,7 @@ Scheduling
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
@@ -88,6 +89,16 @@ class Val(object):
 
     def __init__(self, act, bn=None, relu=False):
         self.act, self.bn, self.relu = act, bn, relu
+
+
+# The tape: one record per forward step; the backward pass walks it in reverse. `lane`: the lane the backward of the
+# entry works on (the forward lane, but for the batched fuse sums: _hr_module).
+ConvEntry = namedtuple('ConvEntry', 'lane xin crec stride y bnrec')
+SumEntry = namedtuple('SumEntry', 'lane terms shifts relu_out out')
+CatEntry = namedtuple('CatEntry', 'lane vals cat align')
+HeadMixEntry = namedtuple('HeadMixEntry', 'lane vals crec y bnrec ts offs align')
+# a fork (or join) of the side `lanes` from lane 0; sums: the pair around the fuse sums of a HighResolutionModule
+LaneMark = namedtuple('LaneMark', 'lane fork lanes sums')
 
 
 class BNRec(object):
@@ -242,7 +253,6 @@ class Plan(object):
         self.max_bwd_part = 0
         self.pending = []         # (program, op_index, slot, kind) scratch pointers to patch
         self.bucket_marks = []    # backward op indices after which a gradient bucket is complete
-        self.tape_lanes = []
         self.nlanes = 4 if _knob('HRNET_LANES', '1') != '0' else 1   # module branches
         # weight-gradient lane (off by default): '2' = only the weight gradients of lane 0 (the high-resolution
         # branch, whose HBM-bound elementwise passes make it the critical chain) move to their own lane; '1' =
@@ -275,9 +285,12 @@ class Plan(object):
     def _scratch(self, prog, idx, slot, kind):
         self.pending.append((prog, idx, slot, kind))
 
-    def _tape(self, entry):
-        self.tape.append(entry)
-        self.tape_lanes.append(self.fwd.lane)
+    def _device_table(self, arr):
+        """a ctypes struct array as a device table that lives as long as the plan"""
+        raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
+        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
+        self.keep.append(table)
+        return table
 
     # ---- forward recording -------------------------------------------------------------
     def conv(self, xin, crec, stride=1, bnrec=None, relu=False, name=None):
@@ -343,7 +356,7 @@ class Plan(object):
                 self.bn_finalize_list.append(bnrec)      # one table-driven launch at the end of the pass
             elif self.training:
                 self._bn_finalize(bnrec, tiles, y.pixels)
-        self._tape(('conv', xin, crec, stride, y, bnrec))
+        self.tape.append(ConvEntry(self.fwd.lane, xin, crec, stride, y, bnrec))
         return Val(y, bnrec, relu)
 
     def _bn_finalize(self, bnrec, rows, count):
@@ -357,9 +370,9 @@ class Plan(object):
                                   save_invstd=C.ptr(bnrec.invstd)))
         self._scratch(self.fwd, j, ops.slot(C.OP_BN_FINALIZE, 'p', 'stats'), 'stats')
 
-    def sum(self, terms, shifts, relu_out, name, batch=None):
+    def sum(self, terms, shifts, relu_out, name, batch=None, lane=None):
         """batch: a list - the op is appended to it as a job of a table-driven launch (HR_OP_EW_TABLE) instead of
-        being emitted as a launch of its own"""
+        being emitted as a launch of its own; lane: the lane the backward pass works this sum on (None: the current one)"""
         t0 = terms[0].act
         sh0 = shifts[0]
         out = self._act(name, t0.N, t0.H << sh0, t0.W << sh0, t0.C)
@@ -391,7 +404,7 @@ class Plan(object):
             self.fwd.add(op)
         for t in terms:
             t.act.nuse += 1
-        self._tape(('sum', list(terms), list(shifts), relu_out, out))
+        self.tape.append(SumEntry(self.fwd.lane if lane is None else lane, list(terms), list(shifts), relu_out, out))
         return Val(out)
 
     def _flush_pending_sum(self, lane=None):
@@ -412,7 +425,7 @@ class Plan(object):
         for v in vals:
             assert v.bn is None and not v.relu
             v.act.nuse += 1
-        self._tape(('cat', list(vals), cat, align))
+        self.tape.append(CatEntry(self.fwd.lane, list(vals), cat, align))
         return Val(cat)
 
     def head_mix(self, vals, crec, bnrec, align=False):
@@ -458,7 +471,7 @@ class Plan(object):
                 self.bn_finalize_list.append(bnrec)
             elif self.training:
                 self._bn_finalize(bnrec, rows, y.pixels)
-        self._tape(('headmix', list(vals), crec, y, bnrec, ts, offs, align))
+        self.tape.append(HeadMixEntry(self.fwd.lane, list(vals), crec, y, bnrec, ts, offs, align))
         self.n_head_mix = 1
         self._head_y = y
         return Val(y, bnrec, True)
@@ -478,29 +491,7 @@ class Plan(object):
         self.n_fused_sums = 0
         self.n_batched_fwd_sums = 0
         self.fwd.before_add = self._flush_pending_sum
-        # Consumer-side BatchNorm (training): producers add their batch sums into 8 partial copies per BatchNorm with
-        # float atomics, forward consumers build scale/shift from them on the fly, and ONE table-driven launch at the
-        # end of the pass fills the arrays the backward pass reads and updates the running statistics - instead of a
-        # finalize launch after each of the 306 convs. HRNET_DETERMINISTIC=1: per-workgroup rows + a finalize launch
-        # per BatchNorm (bit-reproducible statistics).
-        contiguous = all(b.mod.bias.data_ptr() == b.mod.weight.data_ptr() + 4 * b.C for b in self.bns.values())
-        # capacity of the on-the-fly coefficient tables: 768 channels in the conv prologues (HR_CONV_MAXC: the head's
-        # 480 / 720), 384 in hrnet_sum_terms (SUM_MAXC: the widest BatchNorm that reaches a sum is a branch width -
-        # the head's BatchNorm is read by a conv); wider nets fall back to per-BatchNorm finalize launches
-        sum_w = max([b.C for n, b in self.bns.items() if not n.startswith('last_layer')] or [0])
-        self.bn_sums = (self.training and contiguous and _knob('HRNET_DETERMINISTIC', '0') != '1'
-                        and max(b.C for b in self.bns.values()) <= 768 and sum_w <= 384)
-        self.bn_finalize_list = []
-        if self.bn_sums:
-            total = sum(16 * b.C for b in self.bns.values())
-            self.bn_arena = self._f32(total, zero=True)
-            off = 0
-            for b in self.bns.values():
-                b.sums = self.bn_arena[off:off + 16 * b.C]
-                off += 16 * b.C
-            nbytes = total * 4
-            self.fwd.add(ops.make(C.OP_FILL, bytes_lo=ops.u32_bits(nbytes & 0xffffffff), bytes_hi=nbytes >> 32,
-                                  dst=C.ptr(self.bn_arena)))
+        self._setup_batch_sums()
         cv, bn = net.convs, self.bns
         if not self.training:
             # eval mode: every BatchNorm's affine from its running statistics, ONE table launch (306 launches of
@@ -547,6 +538,46 @@ class Plan(object):
             ys = xs
             if s == 3:
                 inter = ys[0]
+        self._record_head(ys, inter)
+        if self.bn_sums and self.bn_finalize_list:
+            self._add_bn_finalize_table()
+        self._flush_pending_sum()
+        self.fwd.before_add = None
+        if self.need_grad:
+            self._build_backward()
+            if self.wlane:
+                self.bwd.sync(self.wlane, 0)     # all weight gradients done before the optimiser
+        self._resolve_scratch()
+        self.fwd.finalize()
+        self.bwd.finalize()
+
+    def _setup_batch_sums(self):
+        # Consumer-side BatchNorm (training): producers add their batch sums into 8 partial copies per BatchNorm with
+        # float atomics, forward consumers build scale/shift from them on the fly, and ONE table-driven launch at the
+        # end of the pass fills the arrays the backward pass reads and updates the running statistics - instead of a
+        # finalize launch after each of the 306 convs. HRNET_DETERMINISTIC=1: per-workgroup rows + a finalize launch
+        # per BatchNorm (bit-reproducible statistics).
+        contiguous = all(b.mod.bias.data_ptr() == b.mod.weight.data_ptr() + 4 * b.C for b in self.bns.values())
+        # capacity of the on-the-fly coefficient tables: 768 channels in the conv prologues (HR_CONV_MAXC: the head's
+        # 480 / 720), 384 in hrnet_sum_terms (SUM_MAXC: the widest BatchNorm that reaches a sum is a branch width -
+        # the head's BatchNorm is read by a conv); wider nets fall back to per-BatchNorm finalize launches
+        sum_w = max([b.C for n, b in self.bns.items() if not n.startswith('last_layer')] or [0])
+        self.bn_sums = (self.training and contiguous and _knob('HRNET_DETERMINISTIC', '0') != '1'
+                        and max(b.C for b in self.bns.values()) <= 768 and sum_w <= 384)
+        self.bn_finalize_list = []
+        if self.bn_sums:
+            total = sum(16 * b.C for b in self.bns.values())
+            self.bn_arena = self._f32(total, zero=True)
+            off = 0
+            for b in self.bns.values():
+                b.sums = self.bn_arena[off:off + 16 * b.C]
+                off += 16 * b.C
+            nbytes = total * 4
+            self.fwd.add(ops.make(C.OP_FILL, bytes_lo=ops.u32_bits(nbytes & 0xffffffff), bytes_hi=nbytes >> 32,
+                                  dst=C.ptr(self.bn_arena)))
+
+    def _record_head(self, ys, inter):
+        net, cv, bn, N = self.net, self.net.convs, self.bns, self.N
         # pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:499-506): align_corners=True, inter_feat = the concat
         # The head: last_layer[0] commutes with the bilinear upsampling, so (bf16, widths the mix launch takes) the
         # 480-channel concat and its gradient are never formed - head_mix(). HRNET_HEAD_MIX=0, the fp32 device path
@@ -574,17 +605,6 @@ class Plan(object):
                                             cp=out.act.C, c=self.nj, src=C.ptr(out.act.t)))
         self.inter_op = self.fwd.add(ops.make(C.OP_NHWC_TO_NCHW, dtype=self.dtid, n=N, h=inter.act.H, w=inter.act.W,
                                               cp=inter.act.C, c=inter.act.C, src=C.ptr(inter.act.t)))
-        if self.bn_sums and self.bn_finalize_list:
-            self._add_bn_finalize_table()
-        self._flush_pending_sum()
-        self.fwd.before_add = None
-        if self.need_grad:
-            self._build_backward()
-            if self.wlane:
-                self.bwd.sync(self.wlane, 0)     # all weight gradients done before the optimiser
-        self._resolve_scratch()
-        self.fwd.finalize()
-        self.bwd.finalize()
 
     def _add_bn_finalize_table(self, eval_mode=False):
         ents = (C.HrBnEnt * len(self.bn_finalize_list))()
@@ -599,11 +619,9 @@ class Plan(object):
             e.momentum, e.eps = (m.momentum if m.momentum is not None else 0.1), m.eps
             e.C, e.block0 = b.C, block
             block += (b.C + 255) // 256
-        raw = bytes(ctypes.string_at(ctypes.addressof(ents), ctypes.sizeof(ents)))
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-        self.keep.append(table)
         self.fwd.lane = 0
-        self.fwd.add(ops.make(C.OP_BN_FINALIZE_TABLE, n=len(self.bn_finalize_list), blocks=block, table=C.ptr(table)))
+        self.fwd.add(ops.make(C.OP_BN_FINALIZE_TABLE, n=len(self.bn_finalize_list), blocks=block,
+                              table=C.ptr(self._device_table(ents))))
 
     def _hr_module(self, xs, pre, num_blocks):
         """HighResolutionModule.forward, pose_hrnet.py:247-266."""
@@ -613,7 +631,7 @@ class Plan(object):
         side = [i for i in range(1, nb) if i < self.nlanes]
         if side:
             self.fwd.fork(side)
-            self._tape(('fork', side))
+            self.tape.append(LaneMark(self.fwd.lane, fork=True, lanes=side, sums=False))
         # recording order of the branches: lane by lane (every block of branch 0, then branch 1 ...), or - HRNET_INTERLEAVE=1,
         # measurement - block by block across the branches, so that the host hands every lane its first launches at once
         # (the programs are enqueued in recording order at ~3.5 us per op)
@@ -633,7 +651,7 @@ class Plan(object):
         if side and not fuse_lanes:
             self.fwd.lane = 0
             self.fwd.join(side)
-            self._tape(('join', side))
+            self.tape.append(LaneMark(self.fwd.lane, fork=False, lanes=side, sums=False))
         term_of = {}
         for j in range(nb):
             if fuse_lanes:
@@ -653,19 +671,19 @@ class Plan(object):
         self.fwd.lane = 0
         if side and fuse_lanes:
             self.fwd.join(side)
-            self._tape(('join', side))
+            self.tape.append(LaneMark(self.fwd.lane, fork=False, lanes=side, sums=False))
         # the sums of the module outputs run on the lane of their output branch (a second fork/join): in the
         # backward pass that spreads a module's 16 sum-term passes over the lanes, and every consumer of a
         # branch gradient sits on that branch's lane
         sum_lanes = side and fuse_lanes and _knob('HRNET_SUM_LANES', '1') != '0'
         # ... or, forward (HRNET_BATCH_SUMFWD, default on): the nb sums as ONE table-driven launch on lane 0 - they are
         # 10-30 us each, and the fork / join around them cost more than running them side by side saved. The tape
-        # keeps the ('fork' / 'join', side, 'sums') markers: the backward pass batches its side of them the same way.
+        # keeps the fork / join marks (sums=True): the backward pass batches its side of them the same way.
         batch = [] if (sum_lanes and _knob('HRNET_BATCH_SUMFWD', '1') != '0') else None
         if sum_lanes:
             if batch is None:
                 self.fwd.fork(side)
-            self._tape(('fork', side, 'sums'))
+            self.tape.append(LaneMark(self.fwd.lane, fork=True, lanes=side, sums=True))
         outs = []
         for i in range(nb):
             if sum_lanes and batch is None:
@@ -674,10 +692,10 @@ class Plan(object):
             shifts = [term_of[(i, j)][1] for j in range(nb)]
             # the output-resolution term first (sum_terms sizes the output from term 0)
             order = sorted(range(nb), key=lambda q: shifts[q])
+            # (batched: recorded on lane 0, but the backward pass works this branch on its own lane)
             outs.append(self.sum([terms[q] for q in order], [shifts[q] for q in order], True,
-                                 '{}.fuse.{}'.format(pre, i), batch=batch))
-            if batch is not None:
-                self.tape_lanes[-1] = i if i in side else 0      # (the lane the backward pass works this branch on)
+                                 '{}.fuse.{}'.format(pre, i), batch=batch,
+                                 lane=None if batch is None else (i if i in side else 0)))
         self.fwd.lane = 0
         if batch:
             sums = any(op.i[ops.slot(C.OP_SUM_TERMS, 'i', 'sums_mode')] for op in batch)
@@ -686,7 +704,7 @@ class Plan(object):
         if sum_lanes:
             if batch is None:
                 self.fwd.join(side)
-            self._tape(('join', side, 'sums'))
+            self.tape.append(LaneMark(self.fwd.lane, fork=False, lanes=side, sums=True))
         return outs
 
     def _add_ew_table(self, prog, kind, jobs, **fields):
@@ -704,10 +722,7 @@ class Plan(object):
                             op.i[dims['W']] >> sh, op.i[dims['C']])
             ops.set_job_blocks(op, block, nb)
             block += nb
-        arr = (C.HrOp * len(jobs))(*jobs)
-        raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-        self.keep.append(table)
+        table = self._device_table((C.HrOp * len(jobs))(*jobs))
         prog.add(ops.make(C.OP_EW_TABLE, jobs=len(jobs), blocks=block, kind=kind, dtype=self.dtid, table=C.ptr(table),
                           **fields))
 
@@ -790,12 +805,53 @@ class Plan(object):
                 self.n_batched_jobs += len(jobs)
 
     def _build_backward(self):
-        net = self.net
+        """the backward program: the tape in reverse, one method per entry kind"""
         # d(heatmaps) NCHW f32 -> NHWC grad of the final conv; d(inter_feat) likewise (optional)
         oa = self.out_act
         self.gout_op = self.bwd.add(ops.make(C.OP_NCHW_TO_NHWC, dtype=self.dtid, n=oa.N, h=oa.H, w=oa.W, cp=oa.C,
                                              c=self.nj, dst=C.ptr(oa.g)))
         oa.ginit = True
+        self._backward_settings()
+        self._scan_tape()
+        self._in_region = False        # between the backward fork and join of a module's lanes
+        self._first_fork = next((i for i, e in enumerate(self.tape) if isinstance(e, LaneMark) and e.fork), None)
+        fused_at, fused_skip = self._find_fused_blocks(), set()
+        self.n_fused_blocks = len(fused_at)
+        self._fused_out_ids = {id(self.tape[ti].out) for ti in fused_at}     # block outputs a fused launch consumes
+        for ti in reversed(range(len(self.tape))):
+            e = self.tape[ti]
+            self.bwd.lane = e.lane
+            if ti in fused_skip:
+                continue
+            if ti in fused_at:
+                self._inter_grad_joins_at(e.out)
+                if fused_at[ti] == 'basic':
+                    self._fused_block_backward(ti)
+                else:
+                    self._fused_bottleneck_backward(ti, downsample=fused_at[ti] == 'bottleneck_ds')
+                fused_skip.update(range(ti - self.FUSED_CONVS[fused_at[ti]], ti))
+            elif isinstance(e, LaneMark):
+                self._lane_mark_backward(ti, e)
+            elif isinstance(e, CatEntry):
+                self._cat_backward(e)
+            elif isinstance(e, HeadMixEntry):
+                self._head_mix_backward(e)
+            elif isinstance(e, SumEntry):
+                self._sum_backward(e)
+            else:
+                self._conv_backward(ti, e)
+        if self.batch_wred:
+            for l in sorted(self._wred):
+                self._flush_wred(l)
+            self.bwd.lane = 0
+            late = sorted(set(self._deferred_lanes) | self._offload_lanes)
+            if late:
+                self.bwd.join(late)       # the deferred / offloaded weight gradients (and their slab sums) are done
+            self._upload_wred_tables()
+
+    FUSED_CONVS = {'basic': 2, 'bottleneck': 3, 'bottleneck_ds': 4}     # tape entries a fused block covers before its sum
+
+    def _backward_settings(self):
         # Weight gradients by float atomics (default): every workgroup of a weight-gradient / fused backward launch ADDS
         # its tile straight into the OIHW f32 gradient (3x3 tiles go through LDS so that a wave instruction covers 64
         # consecutive floats) instead of writing a slab per split that a reduce launch reads back: no slabs (1.94 GB
@@ -809,29 +865,6 @@ class Plan(object):
         self.batch_sums = _knob('HRNET_BATCH_SUMBWD', '1') != '0'
         self._batch = None
         self.n_batched_jobs = 0
-        relu_of = {}   # act -> relu flag its consumers apply (uniform per act in this network)
-        for e in self.tape:
-            if e[0] == 'conv':
-                relu_of[id(e[1].act)] = e[1].relu
-            elif e[0] == 'sum':
-                for t in e[1]:
-                    relu_of[id(t.act)] = t.relu
-        # dgrad epilogue fusion of the BN-backward reduction: the dgrad conv that writes the LAST
-        # contribution to an activation gradient gathers (sum dz, sum dz*y) of the BatchNorm behind it.
-        first_use, producer_sum, use_lanes = {}, {}, {}
-        for ti, (e, ln) in enumerate(zip(self.tape, self.tape_lanes)):
-            if e[0] == 'conv':
-                ins = [e[1].act]
-            elif e[0] == 'sum':
-                ins = [t.act for t in e[1]]
-                producer_sum[id(e[4])] = e
-            elif e[0] in ('cat', 'headmix'):
-                ins = [v.act for v in e[1]]
-            else:
-                continue
-            for a in ins:
-                first_use.setdefault(id(a), ti)
-                use_lanes.setdefault(id(a), set()).add(ln)
         # weight-gradient slab sums are batched: every layer keeps its own slab region and ONE table-driven
         # launch per lane segment (or per ~16 MB of gradient on lane 0) sums them
         self.batch_wred = _knob('HRNET_BATCH_WRED', '1') != '0'
@@ -839,13 +872,13 @@ class Plan(object):
         self._wred_tables = []     # (op index, [entries]) patched with the device table at the end
         self._wred_bytes = 0
         self.slab_bytes = 0
-        fuse_stats = self.training and _knob('HRNET_FUSE_BWDSTATS', '1') != '0'
+        # dgrad epilogue fusion of the BN-backward reduction: the dgrad conv that writes the LAST
+        # contribution to an activation gradient gathers (sum dz, sum dz*y) of the BatchNorm behind it.
+        self._fuse_stats = self.training and _knob('HRNET_FUSE_BWDSTATS', '1') != '0'
         self.n_fused_bwdstats = 0
         self._bnrefs = []
         self.n_inline_bnbwd = 0
         self.inter_gop = None
-        in_region = False
-        self._producer_sum = producer_sum
         # Deferred weight gradients: the weight-gradient launches of the HighResolutionModules are off the critical
         # path, and the end of the backward pass (transition1, layer1, the stem: one lane, a third of its wall
         # time) leaves the other lanes idle - so they are recorded when their operands are final but ENQUEUED on
@@ -878,286 +911,313 @@ class Plan(object):
         self._deferred_lanes = []
         self.late_cuts = []        # (backward op index, flat lo, flat hi, lane): late-region groups final on that lane there
         self.n_deferred_wgrads = 0
-        first_fork = next((i for i, e in enumerate(self.tape) if e[0] == 'fork'), None)
-        fused_at, fused_skip = self._find_fused_blocks(), set()
-        self.n_fused_blocks = len(fused_at)
-        self._fused_out_ids = {id(self.tape[ti][4]) for ti in fused_at}     # block outputs a fused launch consumes
-        for ti, (e, lane) in reversed(list(enumerate(zip(self.tape, self.tape_lanes)))):
-            self.bwd.lane = lane
-            if ti in fused_skip:
+
+    def _scan_tape(self):
+        """_relu_of: act -> relu flag its consumers apply (uniform per act in this network); _first_use / _use_lanes:
+        act -> first tape index / lanes that read it (the LAST contribution to its gradient in the backward pass);
+        _producer_sum: act -> the sum entry that wrote it"""
+        self._relu_of, self._first_use, self._use_lanes, self._producer_sum = {}, {}, {}, {}
+        for ti, e in enumerate(self.tape):
+            if isinstance(e, LaneMark):
                 continue
-            if ti in fused_at:
-                if e[4] is self.inter_act and self.inter_gop is None:
-                    self.inter_gop = len(self.bwd)
-                if fused_at[ti] == 'bottleneck':
-                    self._fused_bottleneck_backward(ti, lane, in_region)
-                    fused_skip.update((ti - 1, ti - 2, ti - 3))
-                elif fused_at[ti] == 'bottleneck_ds':
-                    self._fused_bottleneck_backward(ti, lane, in_region, downsample=True)
-                    fused_skip.update((ti - 1, ti - 2, ti - 3, ti - 4))
-                else:
-                    self._fused_block_backward(ti, lane, in_region)
-                    fused_skip.update((ti - 1, ti - 2))
+            reads = [e.xin] if isinstance(e, ConvEntry) else e.terms if isinstance(e, SumEntry) else e.vals
+            if isinstance(e, SumEntry):
+                self._producer_sum[id(e.out)] = e
+            for v in reads:
+                if isinstance(e, (ConvEntry, SumEntry)):
+                    self._relu_of[id(v.act)] = v.relu
+                self._first_use.setdefault(id(v.act), ti)
+                self._use_lanes.setdefault(id(v.act), set()).add(e.lane)
+
+    def _inter_grad_joins_at(self, act):
+        """the optional external gradient of inter_feat joins in front of this op (run_backward cuts the program there)"""
+        if act is self.inter_act and self.inter_gop is None:
+            self.inter_gop = len(self.bwd)
+
+    @staticmethod
+    def _bn_term_of_sum(e):
+        """the term of sum entry `e` a dgrad epilogue may gather BatchNorm-backward sums for: a raw conv output read
+        through its BatchNorm (no ReLU, same resolution) by this sum alone"""
+        return next((t for t, sh in zip(e.terms, e.shifts)
+                     if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu), None)
+
+    def _lane_mark_backward(self, ti, e):
+        """a forward join is the backward fork of the same lanes, and vice versa"""
+        for l in sorted(self._wred):
+            self._flush_wred(l)
+        self.bwd.lane = 0
+        if self.batch_sums and e.sums:
+            # the backward of the module's fuse sums (a dozen reduce / finalize / apply passes over tensors of
+            # a few MB, three or four per lane in a row) runs as three batched launches on lane 0 instead:
+            # no fork / join around it
+            if not e.fork:
+                self._batch = {C.OP_POOL_REDUCE: [], C.OP_BN_BWD_REDUCE: [], C.OP_BN_BWD_FINALIZE: [], C.OP_GRAD_TERM: []}
+            else:
+                self._flush_batch()
+        elif not e.fork:
+            self.bwd.fork(e.lanes)
+        else:
+            self.bwd.join(e.lanes)
+        if e.fork:
+            if self.defer_wgrad and ti == self._first_fork:
+                self._emit_deferred_wgrads()
+            if self.wlane:
+                self.bwd.sync(self.wlane, 0)
+            # every gradient of this module (and of everything after it) is complete here
+            nxt = next((t for t in self.tape[ti + 1:] if isinstance(t, ConvEntry)), None)
+            if nxt is not None and self.batch_wred:
+                self.bucket_marks.append((len(self.bwd), nxt.crec.prefix))
+        self._in_region = not e.fork
+
+    def _cat_backward(self, e):
+        vals, cat = e.vals, e.cat
+        self._inter_grad_joins_at(cat)
+        assert not any(v.act.ginit for v in vals)
+        self.bwd.add(ops.make(C.OP_BILINEAR_CAT_BWD, dtype=self.dtid, nbr=len(vals), n=cat.N, h=cat.H, w=cat.W,
+                              hs=[v.act.H for v in vals], ws=[v.act.W for v in vals],
+                              cs=[v.act.C for v in vals], align=1.0 if e.align else 0.0, cat=C.ptr(cat.g),
+                              x=[C.ptr(v.act.g) for v in vals]))
+        for v in vals:
+            v.act.ginit = True
+
+    def _sum_backward(self, e):
+        out = e.out
+        self._inter_grad_joins_at(out)
+        if not out.ginit:
+            # no consumer produced a gradient (cannot happen for this network)
+            raise RuntimeError('no gradient reaches ' + out.name)
+        mask = C.ptr(out.t) if e.relu_out else None
+        fusable = self._bn_term_of_sum(e)
+        plain = [t for t in e.terms if not (t.act.bn is not None and t.act.nuse == 1)]
+        # one BN term and one identity/accumulating term share dz: written by the same pass
+        paired = (fusable, plain[0]) if fusable is not None and plain else (None, None)
+        pooled = self._pool_reduce(e, mask)
+        for t, sh in zip(e.terms, e.shifts):
+            a = t.act
+            if t is paired[1]:
                 continue
-            if e[0] in ('fork', 'join'):
-                # a forward join is the backward fork of the same lanes, and vice versa
-                for l in sorted(self._wred):
-                    self._flush_wred(l)
-                self.bwd.lane = 0
-                if self.batch_sums and len(e) > 2 and e[2] == 'sums':
-                    # the backward of the module's fuse sums (a dozen reduce / finalize / apply passes over tensors of
-                    # a few MB, three or four per lane in a row) runs as three batched launches on lane 0 instead:
-                    # no fork / join around it
-                    if e[0] == 'join':
-                        self._batch = {C.OP_POOL_REDUCE: [], C.OP_BN_BWD_REDUCE: [], C.OP_BN_BWD_FINALIZE: [], C.OP_GRAD_TERM: []}
-                    else:
-                        self._flush_batch()
-                elif e[0] == 'join':
-                    self.bwd.fork(e[1])
-                else:
-                    self.bwd.join(e[1])
-                if e[0] == 'fork':
-                    if self.defer_wgrad and ti == first_fork:
-                        self._emit_deferred_wgrads()
-                    if self.wlane:
-                        self.bwd.sync(self.wlane, 0)
-                    # every gradient of this module (and of everything after it) is complete here
-                    nxt = next((t for t in self.tape[ti + 1:] if t[0] == 'conv'), None)
-                    if nxt is not None and self.batch_wred:
-                        self.bucket_marks.append((len(self.bwd), nxt[2].prefix))
-                in_region = e[0] == 'join'
-                continue
-            if e[0] == 'cat':
-                _, vals, cat, align = e
-                if cat is self.inter_act and self.inter_gop is None:
-                    self.inter_gop = len(self.bwd)     # optional external gradient of inter_feat joins here
-                assert not any(v.act.ginit for v in vals)
-                self.bwd.add(ops.make(C.OP_BILINEAR_CAT_BWD, dtype=self.dtid, nbr=len(vals), n=cat.N, h=cat.H, w=cat.W,
-                                      hs=[v.act.H for v in vals], ws=[v.act.W for v in vals],
-                                      cs=[v.act.C for v in vals], align=1.0 if align else 0.0, cat=C.ptr(cat.g),
-                                      x=[C.ptr(v.act.g) for v in vals]))
-                for v in vals:
-                    v.act.ginit = True
-            elif e[0] == 'headmix':
-                self._head_mix_backward(e, lane, in_region, relu_of)
-            elif e[0] == 'sum':
-                _, terms, shifts, relu_out, out = e
-                if out is self.inter_act and self.inter_gop is None:
-                    # optional external gradient of inter_feat: slot patched at run time
-                    self.inter_gop = len(self.bwd)
-                if not out.ginit:
-                    # no consumer produced a gradient (cannot happen for this network)
-                    raise RuntimeError('no gradient reaches ' + out.name)
-                mask = C.ptr(out.t) if relu_out else None
-                fusable = [t for t, sh in zip(terms, shifts)
-                           if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu]
-                plain = [t for t, sh in zip(terms, shifts) if not (t.act.bn is not None and t.act.nuse == 1)]
-                # one BN term and one identity/accumulating term share dz: written by the same pass
-                paired = (fusable[0], plain[0]) if fusable and plain else (None, None)
-                # the nearest-up-sampled terms (from the branches below this output): ONE walk over out.g and the mask
-                # pools every level, stores each level's dz and gathers its sums (HR_OP_POOL_REDUCE)
-                pooled = {}
-                ups = sorted([(sh, t) for t, sh in zip(terms, shifts)
-                              if sh > 0 and t.act.bn is not None and t.act.nuse == 1 and self.training and not t.relu
-                              and t.act.bwd_rows is None], key=lambda q: q[0])
-                if (ups and [q[0] for q in ups] == list(range(1, len(ups) + 1)) and len(ups) <= 3
-                        and out.H % (1 << len(ups)) == 0 and out.W % (1 << len(ups)) == 0
-                        and 256 // (out.C // (4 if self.dt == torch.float32 else 8)) >= 4 ** (len(ups) - 1)
-                        and _knob('HRNET_POOL_REDUCE', '1') != '0' and _knob('HRNET_KEEP_DZ', '1') != '0'):
-                    L = len(ups)
-                    pblocks = C.call('hrnet_ew_table_blocks', C.OP_POOL_REDUCE, self.dtid, out.N, out.H >> 1, out.W >> 1, out.C)
-                    for sh, t in ups:
-                        pooled[id(t.act)] = (self._f32(pblocks * 2 * out.C), pblocks)
-                    self._emit(ops.make(C.OP_POOL_REDUCE, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, nlev=L,
-                                        g=C.ptr(out.g), mask=mask, y=[C.ptr(t.act.t) for _, t in ups],
-                                        dz=[C.ptr(t.act.g) for _, t in ups],
-                                        partials=[C.ptr(pooled[id(t.act)][0]) for _, t in ups]))
-                for t, sh in zip(terms, shifts):
-                    a = t.act
-                    if t is paired[1]:
-                        continue
-                    if a.bn is not None and a.nuse == 1 and self.training:
-                        # single consumer: fuse pooling + masks + BatchNorm backward
-                        self._bn_backward(a, C.ptr(out.g), mask, sh, t.relu,
-                                          extra=paired[1].act if t is paired[0] else None, pooled=pooled.get(id(a)))
-                    else:
-                        # accumulate d(post-activation value); BN backward runs at the producer
-                        assert sh == 0
-                        self._emit(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=a.N, h=a.H, w=a.W, c=a.C,
-                                            accumulate=1 if a.ginit else 0, dst=C.ptr(a.g), g=C.ptr(out.g), mask=mask))
-                        a.ginit = True
-            elif e[0] == 'conv':
-                _, xin, crec, stride, y, bnrec = e
-                x = xin.act
-                ks = 1 if crec.stem else crec.ks
-                self.bwd.tags[len(self.bwd)] = crec.prefix
-                if not y.ginit:
-                    raise RuntimeError('no gradient reaches ' + y.name)
-                if bnrec is not None and not y.bn_done:
-                    # y.g holds d(post-activation) summed over consumers -> d(raw), in place
-                    self._bn_backward(y, C.ptr(y.g), None, 0, relu_of.get(id(y), False))
-                w = crec.mod.weight
-                # a bias in front of a batch-statistics BatchNorm has an exactly zero gradient (the BatchNorm-backward
-                # gradient sums to zero over every channel; autograd's value is rounding noise): no pass over dY
-                if crec.mod.bias is not None and not (bnrec is not None and self.training):
-                    blocks = C.call('hrnet_reduce_blocks', 1, 1, y.pixels, y.C)
-                    self.max_bwd_part = max(self.max_bwd_part, blocks * y.C)
-                    i = self.bwd.add(ops.make(C.OP_BIAS_GRAD, dtype=self.dtid, pixels=y.pixels, cp=y.C, c=crec.Cout,
-                                              accumulate=1, dy=C.ptr(y.g), dbias=C.ptr(net.grad_of(crec.mod.bias))))
-                    self._scratch(self.bwd, i, ops.slot(C.OP_BIAS_GRAD, 'p', 'scratch'), 'bwdpart')
-                # the weight gradient is off the critical path: it runs on its own lane once dY is final
-                if self.wlane and (self.wlane_all or lane == 0):
-                    self.bwd.sync(lane, self.wlane)
-                    self.bwd.lane = self.wlane
-                nsplit = C.call('hrnet_wgrad_splits', self.dtid, x.N, y.H, y.W, y.C, x.C, ks, stride)
-                wflops = 2.0 * x.N * y.H * y.W * y.C * x.C * ks * ks
-                deferred = (self.batch_wred and self.defer_wgrad and in_region and first_fork is not None
-                            and ti > first_fork
-                            and (self.defer_branch_wgrads or '.branches.' not in crec.prefix)
-                            and (not self.dp_plan or net.is_late(w))
-                            and self._defer_flops + wflops <= self._defer_budget)
-                if deferred:
-                    self._defer_flops += wflops
-                if deferred and nsplit > 1:
-                    # A deferred launch runs in the background of the single-lane tail: it does not need the
-                    # parallelism of many splits, and every split is a slab written and read back - but it must
-                    # keep ~100 workgroups (the wide w48 layers have few splits to begin with: dividing those
-                    # cost 6 ms per step). measured (w32 B=64, ms/step): divisor 1: 19.97, 2: 19.56, 4: 19.49, 8: 19.97
-                    div = int(_knob('HRNET_DEFER_SPLIT_DIV', '4'))
-                    tiles = C.call('hrnet_wgrad_tiles', self.dtid, x.N, y.H, y.W, y.C, x.C, ks, stride)
-                    per = C.call('hrnet_wgrad_blocks_per_split', self.dtid, y.H, y.W, y.C, x.C, ks, stride)
-                    floor_ = min(nsplit, -(-96 // max(per, 1)))
-                    nsplit = max(1, floor_, nsplit // max(div, 1))
-                    while nsplit > 1 and tiles % nsplit != 0:
-                        nsplit -= 1
-                # (the stem's weights are a flattened 3x3x3 kernel over im2col columns: its slab layout stays)
-                direct = self.batch_wred and self.wgrad_atomic and not crec.stem
-                wgrad = dict(dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, ho=y.H, wo=y.W, cout=y.C, ks=ks, stride=stride,
-                             in_relu=1 if xin.relu else 0, nsplit=nsplit, atomic=1 if direct else 0,
-                             cout_real=crec.Cout, cin_real=crec.Cin, x=C.ptr(x.t), dy=C.ptr(y.g),
-                             in_scale=C.ptr(xin.bn.scale) if xin.bn else None,
-                             in_shift=C.ptr(xin.bn.shift) if xin.bn else None)
-                if direct:
-                    wop = ops.make(C.OP_WGRAD, slabs=C.ptr(net.grad_of(w)), **wgrad)
-                    if deferred:
-                        self._deferred.append((wop, None, wflops, net.offsets[id(w)][0]))
-                    elif self.offload_wgrad and lane == 0 and not in_region:
-                        l = 1 + self._offload_rr % max(1, self.nlanes - 1)
-                        self._offload_rr += 1
-                        self.bwd.sync(0, l)
-                        self.bwd.add(wop, lane=l)
-                        self._offload_lanes.add(l)
-                    else:
-                        self.bwd.add(wop)
-                        if lane == 0:
-                            self._wred_bytes += crec.Cout * crec.Cin * crec.ks * crec.ks * 4
-                elif self.batch_wred:
-                    slabs = self._f32(nsplit * y.C * ks * ks * x.C)
-                    self.slab_bytes += slabs.numel() * 4
-                    wop = ops.make(C.OP_WGRAD, slabs=C.ptr(slabs), **wgrad)
-                    ent = dict(slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w)), nsplit=nsplit, Cout_pad=y.C, Cin_pad=x.C,
-                               ks=crec.ks if crec.stem else ks, Cout=crec.Cout, Cin=crec.Cin, kflat=1 if crec.stem else 0,
-                               accumulate=1)
-                    if deferred:
-                        # x.t, y.g and the BatchNorm coefficients of xin stay untouched until the program ends
-                        self._deferred.append((wop, ent, wflops, net.offsets[id(w)][0]))
-                    elif self.offload_wgrad and lane == 0 and not in_region:
-                        # a single-lane part of the pass (head, transition1, stem): its weight gradients are off the
-                        # dependency chain - they go to a side lane, which idles there (the head) or carries the
-                        # deferred launches (the tail); their gradient is complete at the end of the program
-                        l = 1 + self._offload_rr % max(1, self.nlanes - 1)
-                        self._offload_rr += 1
-                        self.bwd.sync(0, l)
-                        self.bwd.add(wop, lane=l)
-                        self._wred.setdefault(l, []).append(ent)
-                        self._offload_lanes.add(l)
-                    else:
-                        self.bwd.add(wop)
-                        self._wred.setdefault(self.bwd.lane, []).append(ent)
-                        if lane == 0:
-                            self._wred_bytes += crec.Cout * crec.Cin * crec.ks * crec.ks * 4
-                else:
-                    self.max_slab = max(self.max_slab, nsplit * y.C * ks * ks * x.C)
-                    i = self.bwd.add(ops.make(C.OP_WGRAD, **wgrad))
-                    self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD, 'p', 'slabs'), 'slab')
-                    # (ks: the real taps of the flattened stem kernel)
-                    i = self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=nsplit, cout_pad=y.C, cin_pad=x.C,
-                                              ks=crec.ks if crec.stem else ks, cout=crec.Cout, cin=crec.Cin,
-                                              kflat=1 if crec.stem else 0, accumulate=1, grad=C.ptr(net.grad_of(w))))
-                    self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD_REDUCE, 'p', 'slabs'), 'slab')
-                self.bwd.lane = lane
-                if (x is self._head_y and x.g is not None and xin.bn is not None and self.training and ks == 1
-                        and crec.mod.weight.shape[0] <= y.C and _knob('HRNET_HEAD_BWD', '1') != '0'
-                        and C.call('hrnet_head_mix_supported', self.dtid, y.C, x.C) == 1):
-                    # the layer behind the head's BatchNorm (last_layer.3): its input gradient dz = W^T dY is a K = 32
-                    # product per pixel - formed here only to gather the BatchNorm-backward sums, and formed AGAIN by
-                    # the apply launch in _head_mix_backward (hrnet_head_bwd): dz is never stored or re-read
-                    nrows = C.call('hrnet_head_mix_rows', x.N, x.H, x.W)
-                    rows = self._f32(nrows * 2 * x.C)
-                    self.bwd.add(ops.make(C.OP_HEAD_BWD, dtype=self.dtid, n=x.N, h=x.H, w=x.W, k=y.C, cout=x.C, mode=1,
-                                          inner_relu=1 if xin.relu else 0, dy=C.ptr(y.g), wt=C.ptr(crec.wd), y=C.ptr(x.t),
-                                          out=C.ptr(rows), bn_scale=C.ptr(xin.bn.scale), bn_shift=C.ptr(xin.bn.shift)))
-                    x.bwd_rows = (rows, nrows)
-                    x.ginit = True
-                    self._head_bwd = (y, crec, 1 if xin.relu else 0)
-                    self.n_fused_bwdstats += 1
-                elif x.g is not None:
-                    # input gradient = conv of dY with the transposed kernel (zero-stuffed for stride 2)
-                    bs = {}     # backward statistics: the BS_* slots, the rows and the masked store
-                    last = (first_use.get(id(x)) == ti and use_lanes.get(id(x)) == {lane}
-                            and x is not self.inter_act)
-                    target = None
-                    if fuse_stats and last and xin.bn is not None and x.nuse == 1:
-                        # x is a raw conv output read through its BatchNorm (+ReLU) by this conv alone
-                        target = x
-                        bs['bs_y'] = C.ptr(x.t)
-                        if xin.relu:
-                            bs.update(bs_scale=C.ptr(xin.bn.scale), bs_shift=C.ptr(xin.bn.shift))
-                    elif fuse_stats and last and xin.bn is None and id(x) in producer_sum:
-                        # x is the output of a sum: gather for its first plain BatchNorm term
-                        _, terms, shifts, relu_out, _o = producer_sum[id(x)]
-                        cand = [t for t, sh in zip(terms, shifts)
-                                if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu]
-                        if cand:
-                            target = cand[0].act
-                            bs.update(bs_y=C.ptr(target.t), bs_mask=C.ptr(x.t) if relu_out else None)
-                    if target is not None:
-                        nrows = C.call('hrnet_conv_rows_bwdstats', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
-                        rows = self._f32(nrows * 2 * x.C)
-                        bs['stats'] = C.ptr(rows)
-                        target.bwd_rows = (rows, nrows)
-                        self.n_fused_bwdstats += 1
-                        if (target is not x and bs.get('bs_mask') is not None and id(x) in self._fused_out_ids
-                                and _knob('HRNET_BS_STORE_MASKED', '1') != '0'):
-                            # x closes a block whose backward is a fused launch: this (last) contribution stores the
-                            # gradient already multiplied by x's ReLU mask - no separate mask pass over the tensor
-                            bs['bs_store_masked'] = 1
-                        # (a backward-statistics launch is bound to the kernel family its rows buffer was sized for)
-                        bs['route'] = C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
-                    self.bwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=y.N, h=y.H, w=y.W, cin=y.C, ho=x.H, wo=x.W, cout=x.C,
-                                          ks=ks, stride=stride, upz=1 if stride == 2 else 0,
-                                          accumulate=1 if x.ginit else 0, x=C.ptr(y.g), wgt=C.ptr(crec.wd), y=C.ptr(x.g),
-                                          **bs))
-                    x.ginit = True
-                    if bs.get('bs_store_masked'):
-                        x.gmasked = True
-                if lane == 0 and not in_region:
-                    self._bucket_mark_after_conv(crec)
+            if a.bn is not None and a.nuse == 1 and self.training:
+                # single consumer: fuse pooling + masks + BatchNorm backward
+                self._bn_backward(a, C.ptr(out.g), mask, sh, t.relu,
+                                  extra=paired[1].act if t is paired[0] else None, pooled=pooled.get(id(a)))
+            else:
+                # accumulate d(post-activation value); BN backward runs at the producer
+                assert sh == 0
+                self._emit(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=a.N, h=a.H, w=a.W, c=a.C,
+                                    accumulate=1 if a.ginit else 0, dst=C.ptr(a.g), g=C.ptr(out.g), mask=mask))
+                a.ginit = True
+
+    def _pool_reduce(self, e, mask):
+        """the nearest-up-sampled terms (from the branches below this output): ONE walk over out.g and the mask
+        pools every level, stores each level's dz and gathers its sums (HR_OP_POOL_REDUCE).
+        -> {id(act): (partial rows, blocks)} of the terms it served"""
+        out, pooled = e.out, {}
+        ups = sorted([(sh, t) for t, sh in zip(e.terms, e.shifts)
+                      if sh > 0 and t.act.bn is not None and t.act.nuse == 1 and self.training and not t.relu
+                      and t.act.bwd_rows is None], key=lambda q: q[0])
+        if (ups and [q[0] for q in ups] == list(range(1, len(ups) + 1)) and len(ups) <= 3
+                and out.H % (1 << len(ups)) == 0 and out.W % (1 << len(ups)) == 0
+                and 256 // (out.C // (4 if self.dt == torch.float32 else 8)) >= 4 ** (len(ups) - 1)
+                and _knob('HRNET_POOL_REDUCE', '1') != '0' and _knob('HRNET_KEEP_DZ', '1') != '0'):
+            pblocks = C.call('hrnet_ew_table_blocks', C.OP_POOL_REDUCE, self.dtid, out.N, out.H >> 1, out.W >> 1, out.C)
+            for sh, t in ups:
+                pooled[id(t.act)] = (self._f32(pblocks * 2 * out.C), pblocks)
+            self._emit(ops.make(C.OP_POOL_REDUCE, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, nlev=len(ups),
+                                g=C.ptr(out.g), mask=mask, y=[C.ptr(t.act.t) for _, t in ups],
+                                dz=[C.ptr(t.act.g) for _, t in ups],
+                                partials=[C.ptr(pooled[id(t.act)][0]) for _, t in ups]))
+        return pooled
+
+    # ---- backward of a conv entry: BatchNorm backward, bias gradient, weight gradient, input gradient ----
+    def _conv_backward(self, ti, e):
+        y = e.y
+        self.bwd.tags[len(self.bwd)] = e.crec.prefix
+        if not y.ginit:
+            raise RuntimeError('no gradient reaches ' + y.name)
+        if e.bnrec is not None and not y.bn_done:
+            # y.g holds d(post-activation) summed over consumers -> d(raw), in place
+            self._bn_backward(y, C.ptr(y.g), None, 0, self._relu_of.get(id(y), False))
+        self._bias_grad(e.crec, y, e.bnrec)
+        self._conv_wgrad(ti, e)
+        if not self._head_bwd_stats(e) and e.xin.act.g is not None:
+            self._conv_dgrad(ti, e)
+        self._bucket_mark_after_conv(e.crec, e.lane)
+
+    def _bias_grad(self, crec, y, bnrec):
+        # a bias in front of a batch-statistics BatchNorm has an exactly zero gradient (the BatchNorm-backward
+        # gradient sums to zero over every channel; autograd's value is rounding noise): no pass over dY
+        if crec.mod.bias is None or (bnrec is not None and self.training):
+            return
+        blocks = C.call('hrnet_reduce_blocks', 1, 1, y.pixels, y.C)
+        self.max_bwd_part = max(self.max_bwd_part, blocks * y.C)
+        i = self.bwd.add(ops.make(C.OP_BIAS_GRAD, dtype=self.dtid, pixels=y.pixels, cp=y.C, c=crec.Cout,
+                                  accumulate=1, dy=C.ptr(y.g), dbias=C.ptr(self.net.grad_of(crec.mod.bias))))
+        self._scratch(self.bwd, i, ops.slot(C.OP_BIAS_GRAD, 'p', 'scratch'), 'bwdpart')
+
+    def _conv_wgrad(self, ti, e):
+        net, xin, crec, stride, y, lane = self.net, e.xin, e.crec, e.stride, e.y, e.lane
+        x, w = xin.act, crec.mod.weight
+        ks = 1 if crec.stem else crec.ks
+        # the weight gradient is off the critical path: it runs on its own lane once dY is final
+        if self.wlane and (self.wlane_all or lane == 0):
+            self.bwd.sync(lane, self.wlane)
+            self.bwd.lane = self.wlane
+        nsplit = C.call('hrnet_wgrad_splits', self.dtid, x.N, y.H, y.W, y.C, x.C, ks, stride)
+        wflops = 2.0 * x.N * y.H * y.W * y.C * x.C * ks * ks
+        deferred = (self.batch_wred and self.defer_wgrad and self._in_region and self._first_fork is not None
+                    and ti > self._first_fork
+                    and (self.defer_branch_wgrads or '.branches.' not in crec.prefix)
+                    and (not self.dp_plan or net.is_late(w))
+                    and self._defer_flops + wflops <= self._defer_budget)
+        if deferred:
+            self._defer_flops += wflops
+        if deferred and nsplit > 1:
+            nsplit = self._deferred_splits(nsplit, x, y, ks, stride)
+        # (the stem's weights are a flattened 3x3x3 kernel over im2col columns: its slab layout stays)
+        direct = self.batch_wred and self.wgrad_atomic and not crec.stem
+        wgrad = dict(dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, ho=y.H, wo=y.W, cout=y.C, ks=ks, stride=stride,
+                     in_relu=1 if xin.relu else 0, nsplit=nsplit, atomic=1 if direct else 0,
+                     cout_real=crec.Cout, cin_real=crec.Cin, x=C.ptr(x.t), dy=C.ptr(y.g),
+                     in_scale=C.ptr(xin.bn.scale) if xin.bn else None,
+                     in_shift=C.ptr(xin.bn.shift) if xin.bn else None)
         if self.batch_wred:
-            for l in sorted(self._wred):
-                self._flush_wred(l)
-            self.bwd.lane = 0
-            late = sorted(set(self._deferred_lanes) | self._offload_lanes)
-            if late:
-                self.bwd.join(late)       # the deferred / offloaded weight gradients (and their slab sums) are done
-            self._upload_wred_tables()
+            slabs, ent = net.grad_of(w), None        # (atomic: the launch adds into the OIHW gradient itself)
+            if not direct:
+                slabs = self._f32(nsplit * y.C * ks * ks * x.C)
+                self.slab_bytes += slabs.numel() * 4
+                ent = dict(slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w)), nsplit=nsplit, Cout_pad=y.C, Cin_pad=x.C,
+                           ks=crec.ks if crec.stem else ks, Cout=crec.Cout, Cin=crec.Cin,
+                           kflat=1 if crec.stem else 0, accumulate=1)
+            self._place_wgrad(ops.make(C.OP_WGRAD, slabs=C.ptr(slabs), **wgrad), ent, wflops, crec, lane, deferred)
+        else:
+            self.max_slab = max(self.max_slab, nsplit * y.C * ks * ks * x.C)
+            i = self.bwd.add(ops.make(C.OP_WGRAD, **wgrad))
+            self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD, 'p', 'slabs'), 'slab')
+            # (ks: the real taps of the flattened stem kernel)
+            i = self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=nsplit, cout_pad=y.C, cin_pad=x.C,
+                                      ks=crec.ks if crec.stem else ks, cout=crec.Cout, cin=crec.Cin,
+                                      kflat=1 if crec.stem else 0, accumulate=1, grad=C.ptr(net.grad_of(w))))
+            self._scratch(self.bwd, i, ops.slot(C.OP_WGRAD_REDUCE, 'p', 'slabs'), 'slab')
+        self.bwd.lane = lane
+
+    def _deferred_splits(self, nsplit, x, y, ks, stride):
+        # A deferred launch runs in the background of the single-lane tail: it does not need the
+        # parallelism of many splits, and every split is a slab written and read back - but it must
+        # keep ~100 workgroups (the wide w48 layers have few splits to begin with: dividing those
+        # cost 6 ms per step). measured (w32 B=64, ms/step): divisor 1: 19.97, 2: 19.56, 4: 19.49, 8: 19.97
+        div = int(_knob('HRNET_DEFER_SPLIT_DIV', '4'))
+        tiles = C.call('hrnet_wgrad_tiles', self.dtid, x.N, y.H, y.W, y.C, x.C, ks, stride)
+        per = C.call('hrnet_wgrad_blocks_per_split', self.dtid, y.H, y.W, y.C, x.C, ks, stride)
+        floor_ = min(nsplit, -(-96 // max(per, 1)))
+        nsplit = max(1, floor_, nsplit // max(div, 1))
+        while nsplit > 1 and tiles % nsplit != 0:
+            nsplit -= 1
+        return nsplit
+
+    def _offload_lane(self):
+        """the next side lane (round robin) for a launch that leaves lane 0, ordered behind what lane 0 holds so far"""
+        l = 1 + self._offload_rr % max(1, self.nlanes - 1)
+        self._offload_rr += 1
+        self.bwd.sync(0, l)
+        self._offload_lanes.add(l)
+        return l
+
+    def _count_wgrad_bytes(self, crec, lane):
+        if lane == 0:
+            self._wred_bytes += crec.Cout * crec.Cin * crec.ks * crec.ks * 4      # (towards the next bucket mark)
+
+    def _place_wgrad(self, wop, ent, wflops, crec, lane, deferred):
+        """where weight-gradient launch `wop` runs; ent: the HrWredEnt fields of its slab sum (None: the atomic form)"""
+        if deferred:
+            # x.t, y.g and the BatchNorm coefficients of xin stay untouched until the program ends
+            self._deferred.append((wop, ent, wflops, self.net.offsets[id(crec.mod.weight)][0]))
+            return
+        if self.offload_wgrad and lane == 0 and not self._in_region:
+            # a single-lane part of the pass (head, transition1, stem): its weight gradients are off the
+            # dependency chain - they go to a side lane, which idles there (the head) or carries the
+            # deferred launches (the tail); their gradient is complete at the end of the program
+            l = self._offload_lane()
+            self.bwd.add(wop, lane=l)
+        else:
+            l = self.bwd.lane
+            self.bwd.add(wop)
+            self._count_wgrad_bytes(crec, lane)
+        if ent is not None:
+            self._wred.setdefault(l, []).append(ent)
+
+    def _head_bwd_stats(self, e):
+        """the layer behind the head's BatchNorm (last_layer.3): its input gradient dz = W^T dY is a K = 32
+        product per pixel - formed here only to gather the BatchNorm-backward sums, and formed AGAIN by
+        the apply launch in _head_mix_backward (hrnet_head_bwd): dz is never stored or re-read.
+        -> whether `e` is that layer (it has no input-gradient launch then)"""
+        xin, crec, y = e.xin, e.crec, e.y
+        x = xin.act
+        if not (x is self._head_y and x.g is not None and xin.bn is not None and self.training
+                and (1 if crec.stem else crec.ks) == 1
+                and crec.mod.weight.shape[0] <= y.C and _knob('HRNET_HEAD_BWD', '1') != '0'
+                and C.call('hrnet_head_mix_supported', self.dtid, y.C, x.C) == 1):
+            return False
+        nrows = C.call('hrnet_head_mix_rows', x.N, x.H, x.W)
+        rows = self._f32(nrows * 2 * x.C)
+        self.bwd.add(ops.make(C.OP_HEAD_BWD, dtype=self.dtid, n=x.N, h=x.H, w=x.W, k=y.C, cout=x.C, mode=1,
+                              inner_relu=1 if xin.relu else 0, dy=C.ptr(y.g), wt=C.ptr(crec.wd), y=C.ptr(x.t),
+                              out=C.ptr(rows), bn_scale=C.ptr(xin.bn.scale), bn_shift=C.ptr(xin.bn.shift)))
+        x.bwd_rows = (rows, nrows)
+        x.ginit = True
+        self._head_bwd = (y, crec, 1 if xin.relu else 0)
+        self.n_fused_bwdstats += 1
+        return True
+
+    def _conv_dgrad(self, ti, e):
+        """input gradient = conv of dY with the transposed kernel (zero-stuffed for stride 2); the launch that writes the
+        last contribution to x.g gathers the BatchNorm-backward sums behind x in its epilogue"""
+        xin, crec, stride, y = e.xin, e.crec, e.stride, e.y
+        x = xin.act
+        ks = 1 if crec.stem else crec.ks
+        bs = {}     # backward statistics: the BS_* slots, the rows and the masked store
+        last = (self._first_use.get(id(x)) == ti and self._use_lanes.get(id(x)) == {e.lane}
+                and x is not self.inter_act)
+        target = None
+        if self._fuse_stats and last and xin.bn is not None and x.nuse == 1:
+            # x is a raw conv output read through its BatchNorm (+ReLU) by this conv alone
+            target = x
+            bs['bs_y'] = C.ptr(x.t)
+            if xin.relu:
+                bs.update(bs_scale=C.ptr(xin.bn.scale), bs_shift=C.ptr(xin.bn.shift))
+        elif self._fuse_stats and last and xin.bn is None and id(x) in self._producer_sum:
+            # x is the output of a sum: gather for its first plain BatchNorm term
+            ps = self._producer_sum[id(x)]
+            term = self._bn_term_of_sum(ps)
+            if term is not None:
+                target = term.act
+                bs.update(bs_y=C.ptr(target.t), bs_mask=C.ptr(x.t) if ps.relu_out else None)
+        if target is not None:
+            nrows = C.call('hrnet_conv_rows_bwdstats', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
+            rows = self._f32(nrows * 2 * x.C)
+            bs['stats'] = C.ptr(rows)
+            target.bwd_rows = (rows, nrows)
+            self.n_fused_bwdstats += 1
+            if (target is not x and bs.get('bs_mask') is not None and id(x) in self._fused_out_ids
+                    and _knob('HRNET_BS_STORE_MASKED', '1') != '0'):
+                # x closes a block whose backward is a fused launch: this (last) contribution stores the
+                # gradient already multiplied by x's ReLU mask - no separate mask pass over the tensor
+                bs['bs_store_masked'] = 1
+            # (a backward-statistics launch is bound to the kernel family its rows buffer was sized for)
+            bs['route'] = C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y.C, x.C, ks, stride)
+        self.bwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=y.N, h=y.H, w=y.W, cin=y.C, ho=x.H, wo=x.W, cout=x.C,
+                              ks=ks, stride=stride, upz=1 if stride == 2 else 0,
+                              accumulate=1 if x.ginit else 0, x=C.ptr(y.g), wgt=C.ptr(crec.wd), y=C.ptr(x.g),
+                              **bs))
+        x.ginit = True
+        if bs.get('bs_store_masked'):
+            x.gmasked = True
 
     # ---- backward of the head without its concat (head_mix) ----
-    def _head_mix_backward(self, e, lane, in_region, relu_of):
+    def _head_mix_backward(self, e):
         """G = d(raw y) (BatchNorm backward in place); g_j = up^T(G) at branch j's resolution (hrnet_upsample_bilinear_t);
         dW[:, slice j] = g_j^T x_j and dx_j = W_j^T g_j as 1x1 launches at branch resolution (g_0 = G, full resolution
         with K = C0): autograd of pose_hrnet.py:560-566, an eighth of the concat form's FLOPs"""
-        _, vals, crec, y, bnrec, ts, offs, align = e
+        lane, vals, crec, y, bnrec, ts, offs, align = e.lane, e.vals, e.crec, e.y, e.bnrec, e.ts, e.offs, e.align
         net = self.net
         self.bwd.tags[len(self.bwd)] = crec.prefix
         if not y.ginit:
@@ -1173,21 +1233,15 @@ class Plan(object):
                                   bn_scale=C.ptr(b.scale), bn_shift=C.ptr(b.shift), coef=C.ptr(b.coef)))
             y.bn_done = True
         elif bnrec is not None and not y.bn_done:
-            self._bn_backward(y, C.ptr(y.g), None, 0, relu_of.get(id(y), False))
-        w = crec.mod.weight
-        if crec.mod.bias is not None and not (bnrec is not None and self.training):
-            blocks = C.call('hrnet_reduce_blocks', 1, 1, y.pixels, y.C)
-            self.max_bwd_part = max(self.max_bwd_part, blocks * y.C)
-            i = self.bwd.add(ops.make(C.OP_BIAS_GRAD, dtype=self.dtid, pixels=y.pixels, cp=y.C, c=crec.Cout,
-                                      accumulate=1, dy=C.ptr(y.g), dbias=C.ptr(net.grad_of(crec.mod.bias))))
-            self._scratch(self.bwd, i, ops.slot(C.OP_BIAS_GRAD, 'p', 'scratch'), 'bwdpart')
+            self._bn_backward(y, C.ptr(y.g), None, 0, self._relu_of.get(id(y), False))
+        self._bias_grad(crec, y, bnrec)
         if ts:
             self.bwd.add(ops.make(C.OP_UPSAMPLE_T, dtype=self.dtid, n=y.N, h=y.H, w=y.W, c=y.C, nout=len(ts),
                                   align=1 if align else 0, out_h=[t.H for t in ts], out_w=[t.W for t in ts],
                                   g=C.ptr(y.g), out=[C.ptr(t.g) for t in ts]))
             for t in ts:
                 t.ginit = True
-        gw = net.grad_of(w)
+        gw = net.grad_of(crec.mod.weight)
         direct = self.batch_wred and self.wgrad_atomic
         for j, v in enumerate(vals):
             x = v.act
@@ -1199,12 +1253,7 @@ class Plan(object):
             wgrad = dict(dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=x.C, ho=x.H, wo=x.W, cout=y.C, ks=1, stride=1,
                          nsplit=nsplit, atomic=1 if direct else 0, cout_real=crec.Cout, cin_real=cj,
                          ld=crec.Cin if direct else 0, x=C.ptr(x.t), dy=C.ptr(dy))
-            side = None
-            if self.offload_wgrad and lane == 0 and not in_region:
-                side = 1 + self._offload_rr % max(1, self.nlanes - 1)
-                self._offload_rr += 1
-                self.bwd.sync(0, side)
-                self._offload_lanes.add(side)
+            side = self._offload_lane() if (self.offload_wgrad and lane == 0 and not self._in_region) else None
             if direct:
                 self.bwd.add(ops.make(C.OP_WGRAD, slabs=gptr, **wgrad), lane=side)
             elif self.batch_wred:
@@ -1229,117 +1278,89 @@ class Plan(object):
                 self.bwd.add(ops.make(C.OP_CONV, dtype=self.dtid, n=x.N, h=x.H, w=x.W, cin=y.C, ho=x.H, wo=x.W, cout=x.C,
                                       ks=1, stride=1, accumulate=1 if x.ginit else 0, x=C.ptr(dy), wgt=wd, y=C.ptr(x.g)))
                 x.ginit = True
-        if lane == 0 and not in_region:
-            self._bucket_mark_after_conv(crec)
+        self._bucket_mark_after_conv(crec, lane)
 
     # ---- fused backward of a BasicBlock (conv3x3+BN+ReLU, conv3x3+BN, +x, ReLU: pose_hrnet.py:41-57) ----
     def _find_fused_blocks(self):
-        """tape indices of the 'sum' entries that close a BasicBlock (or an identity Bottleneck) all of whose convs
-        the fused kernels serve -> 'basic' / 'bottleneck'"""
+        """tape indices of the 'sum' entries that close a BasicBlock (or a Bottleneck) all of whose convs the fused
+        kernels serve -> 'basic' / 'bottleneck' / 'bottleneck_ds'"""
         out = {}
         if not self.training or _knob('HRNET_FUSED_BWD', '1') == '0':
             return out
-        T, L = self.tape, self.tape_lanes
         # Widths above 64 (the 128-channel instantiation): only where the LDS-ring pipeline does NOT serve the block's
         # input-gradient convs. w32's 128-channel branch (16x16 maps) has the ring: fused loses there, 19.32 vs 18.82 ms -
         # its four input-channel blocks re-stage the same 128-channel g tile. w48's 96-channel branch (48x36 maps) has
         # only the tile-walking body: fused wins, 28.72 vs 29.92 ms/step (round 4).
         maxc = int(_knob('HRNET_FUSED_MAXC', '128'))     # (tests: restrict the fused path to narrow layers)
+        pointwise = _knob('HRNET_FUSED_PW', '1') != '0'
 
-        def wide_ok(x, y1, y2):
-            if max(x.C, y1.C, y2.C) <= 64:
-                return True
-            return (C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y1.C, x.C, 3, 1) != 2
-                    and C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, y2.C, y1.C, 3, 1) != 2)
-        for ti in range(2, len(T)):
-            e = T[ti]
-            if e[0] != 'sum' or T[ti - 1][0] != 'conv' or T[ti - 2][0] != 'conv':
+        def route(x, cout, cin):
+            return C.call('hrnet_conv_route', self.dtid, x.N, x.H, x.W, cout, cin, 3, 1)
+
+        def fused3(cin, cout):
+            return C.call('hrnet_bwd_fused_supported', self.dtid, cin, cout)
+
+        def fused1(cin, cout):
+            return C.call('hrnet_bwd_pw_supported', self.dtid, cin, cout)
+        for ti, e in enumerate(self.tape):
+            basic = self._block_chain(ti, (3, 3))
+            neck = self._block_chain(ti, (1, 3, 1)) if pointwise else None
+            neck_ds = self._block_chain(ti, (1, 3, 1), behind=1) if pointwise else None
+            chain = basic or neck or neck_ds
+            if not chain:
                 continue
-            _, terms, shifts, relu_out, res = e
-            _, xin2, crec2, st2, y2, bn2 = T[ti - 1]
-            _, xin1, crec1, st1, y1, bn1 = T[ti - 2]
-            if not (len(terms) == 2 and list(shifts) == [0, 0] and relu_out and L[ti] == L[ti - 1] == L[ti - 2]):
-                continue
-            c, idt = terms
-            x = xin1.act
-            ok = (c.act is y2 and c.bn is bn2 and bn2 is not None and not c.relu and y2.nuse == 1
-                  and xin2.act is y1 and xin2.bn is bn1 and bn1 is not None and xin2.relu and y1.nuse == 1
-                  and idt.act is x and idt.bn is xin1.bn and idt.relu == xin1.relu and x.nuse == 2
-                  and st1 == 1 and st2 == 1 and crec1.ks == 3 and crec2.ks == 3 and not crec1.stem
-                  and crec1.mod.bias is None and crec2.mod.bias is None and x.g is not None
-                  and max(x.C, y1.C, y2.C) <= maxc and wide_ok(x, y1, y2)
-                  and C.call('hrnet_bwd_fused_supported', self.dtid, x.C, y1.C)
-                  and C.call('hrnet_bwd_fused_supported', self.dtid, y1.C, y2.C))
-            # the mask the kernel applies to the gradient it stores for x is [a > 0], a = the conv's input as staged:
-            # right when x is read through a ReLU, or is the (non-negative) output of a sum that ended in one
+            xin, x, idt = chain[0].xin, chain[0].xin.act, e.terms[1]
+            y1, y2, y3 = chain[0].y, chain[1].y, chain[-1].y
             ps = self._producer_sum.get(id(x))
-            ok = ok and (xin1.relu or (xin1.bn is None and ps is not None and ps[3]))
-            if ok:
-                out[ti] = 'basic'
-        # Bottleneck with an identity residual (pose_hrnet.py:60-105; layer1 blocks 1..3): conv1 1x1, conv2 3x3,
-        # conv3 1x1, + x, ReLU - the pointwise convs through hrnet_conv1x1_bwd_fused
-        if _knob('HRNET_FUSED_PW', '1') != '0':
-            for ti in range(3, len(T)):
-                e = T[ti]
-                if e[0] != 'sum' or any(T[ti - k][0] != 'conv' for k in (1, 2, 3)):
-                    continue
-                _, terms, shifts, relu_out, res = e
-                _, xin3, crec3, st3, y3, bn3 = T[ti - 1]
-                _, xin2, crec2, st2, y2, bn2 = T[ti - 2]
-                _, xin1, crec1, st1, y1, bn1 = T[ti - 3]
-                if not (len(terms) == 2 and list(shifts) == [0, 0] and relu_out
-                        and L[ti] == L[ti - 1] == L[ti - 2] == L[ti - 3]):
-                    continue
-                c, idt = terms
-                x = xin1.act
-                ps = self._producer_sum.get(id(x))
-                ok = (c.act is y3 and c.bn is bn3 and bn3 is not None and not c.relu and y3.nuse == 1
-                      and xin3.act is y2 and xin3.bn is bn2 and bn2 is not None and xin3.relu and y2.nuse == 1
-                      and xin2.act is y1 and xin2.bn is bn1 and bn1 is not None and xin2.relu and y1.nuse == 1
-                      and idt.act is x and idt.bn is None and not idt.relu and xin1.bn is None and x.nuse == 2
-                      and ps is not None and ps[3]
-                      and st1 == st2 == st3 == 1 and (crec1.ks, crec2.ks, crec3.ks) == (1, 3, 1)
-                      and not (crec1.stem or crec2.stem or crec3.stem)
-                      and crec1.mod.bias is None and crec2.mod.bias is None and crec3.mod.bias is None
-                      and x.g is not None and x is not self.inter_act
-                      and C.call('hrnet_bwd_pw_supported', self.dtid, y2.C, y3.C)
-                      and C.call('hrnet_bwd_fused_supported', self.dtid, y1.C, y2.C)
-                      and C.call('hrnet_bwd_pw_supported', self.dtid, x.C, y1.C))
-                if ok:
+            from_relu_sum = xin.bn is None and ps is not None and ps.relu_out
+            if basic:
+                # the mask the kernel applies to the gradient it stores for x is [a > 0], a = the conv's input as staged:
+                # right when x is read through a ReLU, or is the (non-negative) output of a sum that ended in one
+                if (idt.act is x and idt.bn is xin.bn and idt.relu == xin.relu and x.nuse == 2
+                        and max(x.C, y1.C, y2.C) <= maxc
+                        and (max(x.C, y1.C, y2.C) <= 64 or (route(x, y1.C, x.C) != 2 and route(x, y2.C, y1.C) != 2))
+                        and fused3(x.C, y1.C) and fused3(y1.C, y2.C) and (xin.relu or from_relu_sum)):
+                    out[ti] = 'basic'
+            elif neck:
+                # Bottleneck with an identity residual (pose_hrnet.py:60-105; layer1 blocks 1..3): conv1 1x1, conv2 3x3,
+                # conv3 1x1, + x, ReLU - the pointwise convs through hrnet_conv1x1_bwd_fused
+                if (idt.act is x and idt.bn is None and not idt.relu and x.nuse == 2 and from_relu_sum
+                        and x is not self.inter_act
+                        and fused1(y2.C, y3.C) and fused3(y1.C, y2.C) and fused1(x.C, y1.C)):
                     out[ti] = 'bottleneck'
-            # ... and the first Bottleneck of layer1, whose residual is a 1x1 conv + BatchNorm of the same input
-            # (pose_hrnet.py:98-99: downsample): conv1, conv2, conv3, downsample, sum
-            for ti in range(4, len(T)):
-                e = T[ti]
-                if e[0] != 'sum' or any(T[ti - k][0] != 'conv' for k in (1, 2, 3, 4)):
-                    continue
-                _, terms, shifts, relu_out, res = e
-                _, xind, crecd, std, yd, bnd = T[ti - 1]
-                _, xin3, crec3, st3, y3, bn3 = T[ti - 2]
-                _, xin2, crec2, st2, y2, bn2 = T[ti - 3]
-                _, xin1, crec1, st1, y1, bn1 = T[ti - 4]
-                if not (len(terms) == 2 and list(shifts) == [0, 0] and relu_out
-                        and len({L[ti - k] for k in range(5)}) == 1):
-                    continue
-                c, d = terms
-                x = xin1.act
-                ok = (c.act is y3 and c.bn is bn3 and bn3 is not None and not c.relu and y3.nuse == 1
-                      and d.act is yd and d.bn is bnd and bnd is not None and not d.relu and yd.nuse == 1
-                      and xin3.act is y2 and xin3.bn is bn2 and bn2 is not None and xin3.relu and y2.nuse == 1
-                      and xin2.act is y1 and xin2.bn is bn1 and bn1 is not None and xin2.relu and y1.nuse == 1
-                      and xind.act is x and xind.bn is xin1.bn and xind.relu == xin1.relu and xin1.relu
-                      and xin1.bn is not None and x.nuse == 2
-                      and st1 == st2 == st3 == std == 1 and (crec1.ks, crec2.ks, crec3.ks, crecd.ks) == (1, 3, 1, 1)
-                      and not (crec1.stem or crec2.stem or crec3.stem or crecd.stem)
-                      and all(cr.mod.bias is None for cr in (crec1, crec2, crec3, crecd))
-                      and x.g is not None and x is not self.inter_act
-                      and C.call('hrnet_bwd_pw_supported', self.dtid, y2.C, y3.C)
-                      and C.call('hrnet_bwd_pw_supported', self.dtid, x.C, yd.C)
-                      and C.call('hrnet_bwd_fused_supported', self.dtid, y1.C, y2.C)
-                      and C.call('hrnet_bwd_pw_supported', self.dtid, x.C, y1.C))
-                if ok:
+            else:
+                # ... and the first Bottleneck of layer1, whose residual is a 1x1 conv + BatchNorm of the same input
+                # (pose_hrnet.py:98-99: downsample): conv1, conv2, conv3, downsample, sum
+                ds = self.tape[ti - 1]
+                if (idt.act is ds.y and idt.bn is ds.bnrec and ds.bnrec is not None and not idt.relu and ds.y.nuse == 1
+                        and ds.xin.act is x and ds.xin.bn is xin.bn and ds.xin.relu == xin.relu and xin.relu
+                        and xin.bn is not None and x.nuse == 2 and self._plain_conv(ds, 1) and x is not self.inter_act
+                        and fused1(y2.C, y3.C) and fused1(x.C, ds.y.C) and fused3(y1.C, y2.C) and fused1(x.C, y1.C)):
                     out[ti] = 'bottleneck_ds'
         return out
+
+    @staticmethod
+    def _plain_conv(c, ks):
+        """a stride-1 ks x ks conv entry without bias (what the fused backward kernels serve)"""
+        return c.stride == 1 and c.crec.ks == ks and not c.crec.stem and c.crec.mod.bias is None
+
+    def _block_chain(self, ti, kss, behind=0):
+        """the conv entries (forward order) of the residual block the sum entry at `ti` closes, or None: a chain of
+        plain convs of kernel sizes `kss`, each read through its own BatchNorm + ReLU by the next alone and the last
+        through its BatchNorm by the sum's first term alone, then `behind` more convs (the residual's), then the
+        two-term ReLU sum - all on one lane, with a gradient wanted for the block input"""
+        T, n = self.tape, len(kss) + behind
+        e = T[ti]
+        if ti < n or not isinstance(e, SumEntry) or not all(isinstance(c, ConvEntry) for c in T[ti - n:ti]):
+            return None
+        chain, c = T[ti - n:ti - behind], e.terms[0]
+        ok = (len(e.terms) == 2 and list(e.shifts) == [0, 0] and e.relu_out and len({t.lane for t in T[ti - n:ti + 1]}) == 1
+              and c.act is chain[-1].y and c.bn is chain[-1].bnrec and c.bn is not None and not c.relu
+              and chain[-1].y.nuse == 1
+              and all(b.xin.act is a.y and b.xin.bn is a.bnrec and a.bnrec is not None and b.xin.relu and a.y.nuse == 1
+                      for a, b in zip(chain, chain[1:]))
+              and all(self._plain_conv(cv, ks) for cv, ks in zip(chain, kss)) and chain[0].xin.act.g is not None)
+        return chain if ok else None
 
     def _bn_bwd_finalize(self, y, reduce_from=None):
         """coefficients (and dgamma/dbeta) of y's BatchNorm backward from the sums a previous launch left in
@@ -1410,23 +1431,25 @@ class Plan(object):
                               rows=C.ptr(rows), bs_y=C.ptr(rows_for.t) if rows_for is not None else None,
                               slabs=C.ptr(slabs), bnref=ctypes.addressof(ref) if ref is not None else None))
         if atomic:
-            if lane == 0:
-                self._wred_bytes += crec.Cout * crec.Cin * ks * ks * 4
-            return
-        ent = dict(slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w)), nsplit=ns, Cout_pad=y.C, Cin_pad=x.C, ks=ks,
-                   Cout=crec.Cout, Cin=crec.Cin, kflat=0, accumulate=1)
-        if self.batch_wred:
-            self._wred.setdefault(lane, []).append(ent)
-            if lane == 0:
-                self._wred_bytes += crec.Cout * crec.Cin * ks * ks * 4
+            self._count_wgrad_bytes(crec, lane)
+        elif self.batch_wred:
+            self._wred.setdefault(lane, []).append(dict(
+                slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w)), nsplit=ns, Cout_pad=y.C, Cin_pad=x.C, ks=ks,
+                Cout=crec.Cout, Cin=crec.Cin, kflat=0, accumulate=1))
+            self._count_wgrad_bytes(crec, lane)
         else:
             self.bwd.add(ops.make(C.OP_WGRAD_REDUCE, nsplit=ns, cout_pad=y.C, cin_pad=x.C, ks=ks, cout=crec.Cout,
                                   cin=crec.Cin, accumulate=1, slabs=C.ptr(slabs), grad=C.ptr(net.grad_of(w))))
 
     def _mask_gradient(self, out):
-        """out.g *= [out > 0], in place: the ReLU mask the fused launches expect on the gradient they read"""
-        self.bwd.add(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, dst=C.ptr(out.g),
-                              g=C.ptr(out.g), mask=C.ptr(out.t)))
+        """out.g *= [out > 0], in place: the ReLU mask the fused launches expect on the gradient they read (applied
+        once, where the block output's gradient came from unfused consumers)"""
+        if not out.ginit:
+            raise RuntimeError('no gradient reaches ' + out.name)
+        if not out.gmasked:
+            self.bwd.add(ops.make(C.OP_GRAD_TERM, dtype=self.dtid, n=out.N, h=out.H, w=out.W, c=out.C, dst=C.ptr(out.g),
+                                  g=C.ptr(out.g), mask=C.ptr(out.t)))
+            out.gmasked = True
 
     def _rows_target(self, x, xin):
         """the raw activation behind x whose BatchNorm backward needs (sum dz, sum dz*y) of x's gradient"""
@@ -1435,29 +1458,23 @@ class Plan(object):
         if xin.bn is not None:
             return x                             # x is a raw conv output read through its BatchNorm + ReLU
         ps = self._producer_sum.get(id(x))
-        cand = [t for t, sh in zip(ps[1], ps[2])
-                if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu] if ps else []
-        return cand[0].act if cand else None
+        term = self._bn_term_of_sum(ps) if ps is not None else None
+        return term.act if term is not None else None
 
-    def _fused_bottleneck_backward(self, ti, lane, in_region, downsample=False):
+    def _fused_bottleneck_backward(self, ti, downsample=False):
         """Bottleneck: fused launches for conv3 1x1, conv2 3x3, conv1 1x1 (+ the residual stream: the identity's
         masked gradient, or the input gradient of the downsample conv written first)"""
-        _, terms, shifts, relu_out, out = self.tape[ti]
+        out, lane = self.tape[ti].out, self.tape[ti].lane
         k = 1 if downsample else 0
-        _, xin3, crec3, _, y3, bn3 = self.tape[ti - 1 - k]
-        _, xin2, crec2, _, y2, bn2 = self.tape[ti - 2 - k]
-        _, xin1, crec1, _, y1, bn1 = self.tape[ti - 3 - k]
+        c1, c2, c3 = self.tape[ti - 3 - k:ti - k]
+        (xin1, crec1, y1), (xin2, crec2, y2), (xin3, crec3, y3) = [(c.xin, c.crec, c.y) for c in (c1, c2, c3)]
         x = xin1.act
         self.bwd.tags[len(self.bwd)] = crec3.prefix
-        if not out.ginit:
-            raise RuntimeError('no gradient reaches ' + out.name)
         assert not x.ginit and not y1.ginit and not y2.ginit and not y3.ginit
-        if not out.gmasked:
-            self._mask_gradient(out)
-            out.gmasked = True
+        self._mask_gradient(out)
         residual = C.ptr(out.g)              # identity: the masked d(out) joins the input gradient of conv1
         if downsample:
-            _, xind, crecd, _, yd, bnd = self.tape[ti - 1]
+            xind, crecd, yd = self.tape[ti - 1].xin, self.tape[ti - 1].crec, self.tape[ti - 1].y
             assert not yd.ginit
             self.bwd.tags[len(self.bwd)] = crecd.prefix
             self._fused_conv_bwd(C.ptr(out.g), yd, xind, crecd, C.ptr(x.g), None, True, None, lane,
@@ -1479,41 +1496,26 @@ class Plan(object):
         self._fused_conv_bwd(C.ptr(y1.g), y1, xin1, crec1, C.ptr(x.g), residual, True,
                              self._rows_target(x, xin1), lane, reduce_from=C.ptr(y1.g))
         x.ginit = x.gmasked = True
-        if lane == 0 and not in_region:
-            self._bucket_mark_after_conv(crec1)
+        self._bucket_mark_after_conv(crec1, lane)
 
-    def _fused_block_backward(self, ti, lane, in_region):
-        _, terms, shifts, relu_out, out = self.tape[ti]
-        _, xin2, crec2, _, y2, bn2 = self.tape[ti - 1]
-        _, xin1, crec1, _, y1, bn1 = self.tape[ti - 2]
+    def _fused_block_backward(self, ti):
+        out, lane = self.tape[ti].out, self.tape[ti].lane
+        c1, c2 = self.tape[ti - 2:ti]
+        (xin1, crec1, y1), (xin2, crec2, y2) = (c1.xin, c1.crec, c1.y), (c2.xin, c2.crec, c2.y)
         x = xin1.act
         self.bwd.tags[len(self.bwd)] = crec2.prefix
-        if not out.ginit:
-            raise RuntimeError('no gradient reaches ' + out.name)
         assert not x.ginit and not y1.ginit and not y2.ginit
-        if not out.gmasked:
-            # the block output's gradient came from unfused consumers: apply its ReLU mask once, in place
-            self._mask_gradient(out)
-            out.gmasked = True
+        self._mask_gradient(out)
         # conv2: dz = d(out) masked (it is also the identity branch's gradient); its input is relu(bn1(y1))
         self._fused_conv_bwd(C.ptr(out.g), y2, xin2, crec2, C.ptr(y1.g), None, True, y1, lane,
                              reduce_from=C.ptr(out.g))
         y1.ginit = y1.gmasked = True
         y2.ginit = True
         # conv1: its input is the block input x; the residual stream (the masked d(out)) joins before the mask
-        target = None
-        if x is not self.inter_act:
-            if xin1.bn is not None:
-                target = x                       # x is a raw conv output read through its BatchNorm + ReLU
-            else:
-                ps = self._producer_sum.get(id(x))
-                cand = [t for t, sh in zip(ps[1], ps[2])
-                        if t.act.bn is not None and t.act.nuse == 1 and sh == 0 and not t.relu] if ps else []
-                target = cand[0].act if cand else None
-        self._fused_conv_bwd(C.ptr(y1.g), y1, xin1, crec1, C.ptr(x.g), C.ptr(out.g), True, target, lane)
+        self._fused_conv_bwd(C.ptr(y1.g), y1, xin1, crec1, C.ptr(x.g), C.ptr(out.g), True,
+                             self._rows_target(x, xin1), lane)
         x.ginit = x.gmasked = True
-        if lane == 0 and not in_region:
-            self._bucket_mark_after_conv(crec1)
+        self._bucket_mark_after_conv(crec1, lane)
 
     def _emit_deferred_wgrads(self):
         """enqueue the recorded weight-gradient launches on the side lanes (largest first, least-loaded lane)"""
@@ -1571,19 +1573,20 @@ class Plan(object):
         self._deferred = []
         self.bwd.lane = keep
 
-    def _bucket_mark_after_conv(self, crec):
+    def _bucket_mark_after_conv(self, crec, lane):
+        """a bucket mark behind the backward of a layer on the single-lane parts of the pass (batched slab sums: once
+        ~16 MB of weight gradient have gathered)"""
+        if lane != 0 or self._in_region:
+            return
         if self.batch_wred:
-            if self._wred_bytes >= (16 << 20):
-                for l in sorted(self._wred):
-                    self._flush_wred(l)
-                self.bwd.lane = 0
-                if self.wlane:
-                    self.bwd.sync(self.wlane, 0)
-                self.bucket_marks.append((len(self.bwd), crec.prefix))
-        else:
-            if self.wlane:
-                self.bwd.sync(self.wlane, 0)    # this bucket's weight gradients are complete
-            self.bucket_marks.append((len(self.bwd), crec.prefix))
+            if self._wred_bytes < (16 << 20):
+                return
+            for l in sorted(self._wred):
+                self._flush_wred(l)
+            self.bwd.lane = 0
+        if self.wlane:
+            self.bwd.sync(self.wlane, 0)    # this bucket's weight gradients are complete
+        self.bucket_marks.append((len(self.bwd), crec.prefix))
 
     def _flush_wred(self, lane):
         ents = self._wred.pop(lane, None)
@@ -1602,7 +1605,6 @@ class Plan(object):
             self._wred_bytes = 0
 
     def _upload_wred_tables(self):
-        import ctypes
         n = sum(len(e) for _, e in self._wred_tables)
         if not n:
             return
@@ -1615,9 +1617,7 @@ class Plan(object):
                 for name, val in e.items():
                     setattr(arr[k], name, val)
                 k += 1
-        raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
-        table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-        self.keep.append(table)
+        table = self._device_table(arr)
         slot = ops.slot(C.OP_WGRAD_REDUCE_TABLE, 'p', 'table')
         for i, k0 in starts:
             self.bwd.ops[i].p[slot] = C.ptr(table) + k0 * ctypes.sizeof(C.HrWredEnt)
