@@ -39,6 +39,7 @@ struct HeadMixArgs {
   int tiles_x, tiles_y, chunks;
   int wrow;           // LDS bytes per weight row (K * 2 + 16)
   int sl_off;         // LDS byte offset of the per-wave statistics [4][2][HM_CH] floats
+  int cf_off;         // LDS byte offset of this chunk's per-channel epilogue operands [5][HM_CH] floats
   // backward of the layer BEHIND y (hrnet_head_bwd; MODE 1 / 2 of the kernels): x = dY of that layer [N][H][W][K],
   // w = its transposed packed weight [Cout][K], so the product is d(ReLU output) of this layer - never stored
   const char* yin;        // raw y [N][H][W][Cout]
@@ -86,11 +87,12 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
   const int kv = a.K / 8;      // 16-byte vectors per weight row
   constexpr int cvn = HM_CH / 8;
   constexpr int WB = 2, TB = 5;        // loads per thread and batch: weights / one low-resolution tile
+  const int nup = MODE == 0 ? a.nup : 0;      // (the backward modes carry no low-resolution terms)
   int ylo[3], xlo[3], rw[3], tot[3];
 #pragma unroll
   for (int u = 0; u < 3; ++u) {
     ylo[u] = xlo[u] = 0; rw[u] = 1; tot[u] = 0;
-    if (u < a.nup) {
+    if (u < nup) {
       int i0, i1, j0, j1;
       float l;
       bilin_src(Y0, a.uh[u], a.H, a.align, i0, i1, l);
@@ -118,6 +120,27 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
                ? *(const V16*)(src + ((size_t)(ylo[u] + r) * a.uw[u] + xlo[u] + c) * a.Cout * 2 + cv * 16)
                : v16_zero();
   };
+  // the per-channel operands of the epilogue (MODE 0: the bias; MODE 1 / 2: the BatchNorm affine of the ReLU mask and
+  // A, B, C of mode 2) go through LDS once per chunk instead of dependent global loads in front of every sub-block's
+  // epilogue
+  constexpr int NCF = MODE == 0 ? 1 : MODE == 1 ? 2 : 5;
+  float cfv[5] = {MODE == 0 ? 0.f : 1.f, 0.f, 0.f, 0.f, 0.f};
+  {
+    const int n = c_base + tid;
+    if (tid < HM_CH && n < a.Cout) {
+      if constexpr (MODE == 0) {
+        if (a.bias) cfv[0] = a.bias[n];
+      } else {
+        if (a.bn_scale) cfv[0] = a.bn_scale[n];
+        if (a.bn_shift) cfv[1] = a.bn_shift[n];
+        if constexpr (MODE == 2) {
+          cfv[2] = a.coef[n];
+          cfv[3] = a.coef[a.Cout + n];
+          cfv[4] = a.coef[2 * a.Cout + n];
+        }
+      }
+    }
+  }
   {
     V16 wv[WB], tv[3][TB];
 #pragma unroll
@@ -125,7 +148,7 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
 #pragma unroll
     for (int u = 0; u < 3; ++u)
 #pragma unroll
-      for (int q = 0; q < TB; ++q) tv[u][q] = u < a.nup ? tload(u, q * 256 + tid) : v16_zero();
+      for (int q = 0; q < TB; ++q) tv[u][q] = u < nup ? tload(u, q * 256 + tid) : v16_zero();
 #pragma unroll
     for (int q = 0; q < WB; ++q) {
       const int i = q * 256 + tid;
@@ -138,6 +161,11 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
         const int i = q * 256 + tid;
         if (i < tot[u]) *(V16*)(lds + a.toff[u] + (i / cvn) * HM_TROW + (i % cvn) * 16) = tv[u][q];
       }
+  }
+  if (tid < HM_CH) {
+    float* cf = (float*)(lds + a.cf_off);
+#pragma unroll
+    for (int q = 0; q < NCF; ++q) cf[q * HM_CH + tid] = cfv[q];
   }
   // (larger problems: the rest, batch by batch)
   for (int i0 = WB * 256; i0 < wtot; i0 += 256) {
@@ -160,7 +188,7 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
 #pragma unroll
   for (int u = 0; u < 3; ++u) {
     xo0[u] = xdx[u] = 0; xl[u] = 0.f;
-    if (u < a.nup && xok) {
+    if (u < nup && xok) {
       int x0, x1;
       float lx;
       bilin_src(ox, a.uw[u], a.W, a.align, x0, x1, lx);
@@ -179,7 +207,7 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
     rb[u] = 0; nr[u] = 0;
 #pragma unroll
     for (int g = 0; g < 4; ++g) { ry0[u][g] = -1; ry1[u][g] = -1; rwa[u][g] = 0.f; rwb[u][g] = 0.f; }
-    if (u < a.nup) {
+    if (u < nup) {
       int last = 0, first = 0;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -208,14 +236,29 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
   V16 bf0[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) bf0[g] = (pok[g] && lg * 8 < a.K) ? *(const V16*)(xp0 + g * xrow) : v16_zero();
+  // MODE 1 / 2: the raw y of EVERY sub-block's epilogue leaves with the B fragments (12 more 16-byte loads in flight):
+  // loaded in front of each epilogue they were three more dependent round trips per workgroup
+  constexpr int NSB = HM_CH / 32;
+  V16 yall[MODE != 0 ? NSB : 1][4];
+  if constexpr (MODE != 0) {
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int n0 = c_base + sb * 32 + lg * 8;
+        yall[sb][g] = (pok[g] && n0 < a.Cout)
+                          ? *(const V16*)(a.yin + ((((size_t)img * a.H + oy0 + g) * a.W + ox) * a.Cout + n0) * 2)
+                          : v16_zero();
+      }
+  }
   __syncthreads();
 
   float* sl = (float*)(lds + a.sl_off);      // [4 waves][2][HM_CH]
   const bool stats = MODE == 1 || (MODE == 0 && (a.sums != nullptr || a.rows != nullptr));
-#pragma unroll 1
-  for (int sb = 0; sb < HM_CH / 32; ++sb) {
+  // one sub-block of 32 channels; yv = its raw y (MODE 1 / 2)
+  auto sub_block = [&](const int sb, const V16 (&yv)[4]) {
     const int n0 = c_base + sb * 32 + lg * 8;       // this lane's 8 output channels
-    if (c_base + sb * 32 >= a.Cout) break;          // (uniform)
+    if (c_base + sb * 32 >= a.Cout) return;         // (uniform)
     f32x4 acc[2][4];
 #pragma unroll
     for (int f = 0; f < 2; ++f)
@@ -244,7 +287,7 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
     {
       float b8[8];
 #pragma unroll
-      for (int c = 0; c < 8; ++c) b8[c] = (a.bias && n0 + c < a.Cout) ? a.bias[n0 + c] : 0.f;
+      for (int c = 0; c < 8; ++c) b8[c] = MODE == 0 ? ((const float*)(lds + a.cf_off))[sb * 32 + lg * 8 + c] : 0.f;
 #pragma unroll
       for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -253,7 +296,7 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
     const int coff = (sb * 32 + lg * 8) * 2;
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
-      if (u < a.nup) {
+      if (u < nup) {
         const float lx = xl[u], hx = 1.f - lx;
         const char* p = lds + xo0[u] + coff + rb[u] * rw[u] * HM_TROW;
 #pragma unroll
@@ -297,20 +340,16 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
       }
     } else {
       const bool cok = n0 < a.Cout;
-      V16 yv[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        yv[g] = (pok[g] && cok) ? *(const V16*)(a.yin + ((((size_t)img * a.H + oy0 + g) * a.W + ox) * a.Cout + n0) * 2)
-                                : v16_zero();
       float sc[8], sf[8], cA[8], cB[8], cC[8];
+      const float* cf = (const float*)(lds + a.cf_off) + sb * 32 + lg * 8;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        sc[c] = (a.bn_scale && cok) ? a.bn_scale[n0 + c] : 1.f;
-        sf[c] = (a.bn_shift && cok) ? a.bn_shift[n0 + c] : 0.f;
+        sc[c] = cf[0 * HM_CH + c];
+        sf[c] = cf[1 * HM_CH + c];
         if constexpr (MODE == 2) {
-          cA[c] = cok ? a.coef[n0 + c] : 0.f;
-          cB[c] = cok ? a.coef[a.Cout + n0 + c] : 0.f;
-          cC[c] = cok ? a.coef[2 * a.Cout + n0 + c] : 0.f;
+          cA[c] = cf[2 * HM_CH + c];
+          cB[c] = cf[3 * HM_CH + c];
+          cC[c] = cf[4 * HM_CH + c];
         }
       }
 #pragma unroll
@@ -348,6 +387,14 @@ __global__ __launch_bounds__(256, 3) void head_mix_tile_kernel(HeadMixArgs a) {
         }
       }
     }
+  };
+  if constexpr (MODE == 0) {
+#pragma unroll 1
+    for (int sb = 0; sb < NSB; ++sb) sub_block(sb, yall[0]);
+  } else {
+    // (unrolled: yall is indexed statically and stays in registers)
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb) sub_block(sb, yall[sb]);
   }
   if (stats) {
     __syncthreads();
@@ -596,6 +643,205 @@ __global__ __launch_bounds__(256) void upsample_t_tile_kernel(UpTileArgs a) {
   }
 }
 
+// ---- the same, bf16, on the matrix pipe ----
+//   out_s[oh][ow][c] = sum_Y wy_s[oh][Y] * ( sum_X wx_s[ow][X] * G[Y][X][c] )
+// The weights are separable, and the inner sum - the contraction over the pixels of ONE image row - is a matrix
+// product whose weights ((2r + 1) / 2s, or 1 at a clamped border) are exact in bf16. A workgroup stages the 24x24-pixel
+// region around a 16x16 tile (halo 4 = half the largest scale, whatever scales are asked for) for 64 channels; wave v
+// owns 16 of them. Per region row Y ONE 16x16x32 MFMA forms T[Y][ow'][c] for all three scales at once:
+//   A = the row's 24 pixels (+ 8 zeros) x 16 channels, transposed on the way out of LDS (ds_read_b64_tr_b16),
+//   B = wx of the 8 + 4 + 2 low-resolution columns of the tile (column ow' = lane & 15), built once per tile.
+// The contraction over Y stays in f32 on the vector ALU, 4 channels per lane (ow', lg). With u = Y - 4 + s/2 a region
+// row lies in the FIRST half of the footprint of output row u / s, weight f = (u % s + 1/2) / s, and in the SECOND half
+// of row u / s - 1, weight 1 - f (1 where upt_scale's border rule clamps): every lane, whatever its scale, adds T[Y] to
+// two running sums - 8 FMAs per row - and whenever u reaches a multiple of s the older sum is complete: it is stored
+// and the sums move up. That replaces the ~200 LDS reads and lane permutes per thread of the form above; the result
+// differs from it only in the order of the f32 sums. (A non-finite G reaches every low-resolution pixel of its region
+// row: 0 * inf; the forms above confine it to the footprints that hold it.)
+// The grid is sized to the machine (2 workgroups per CU) and walks (tile, channel chunk) jobs; the next job's 18
+// 16-byte loads per thread are in flight while the current one is contracted.
+struct UpMmaArgs {
+  const char* g;      // [N][H][W][C]
+  char* out[3];       // by scale: [0] s = 2, [1] s = 4, [2] s = 8; NULL: not asked for
+  int N, H, W, C;
+  int tiles_x, tiles_y, chunks, njobs;
+  unsigned g_bytes;   // bytes of G (buffer descriptor: 32-bit offsets)
+};
+
+constexpr int UM_HALO = 4, UM_R = HM_T + 2 * UM_HALO;     // staged region edge: 24 pixels
+constexpr int UM_CH = 64, UM_PXB = UM_CH * 2;             // channels per workgroup; LDS bytes per staged pixel
+constexpr int UM_NV = UM_R * UM_R * (UM_CH / 8) / 256;    // 16-byte vectors per thread and job: 18
+constexpr int UM_LDS = (UM_R * UM_R + 8) * UM_PXB;        // 73 KB (8 zero pixels behind the region): two workgroups per CU
+static_assert(UM_R % 8 == 0 && UM_R * UM_R * (UM_CH / 8) % 256 == 0, "region geometry");
+
+// XOR on the byte offset inside a staged pixel (unpadded 128-byte rows), keyed on the pixel's column X in the region:
+// a 32-lane half of a transposing read addresses pixels {X, X+1, X+2, X+3, X+8, .. X+11} x 32 bytes - with the 32-byte
+// pair index XORed by (bit 1 of X, bit 3 of X) they cover the 64 banks once.
+__device__ __forceinline__ int um_swz(int X) { return (((X >> 1) & 1) | (((X >> 3) & 1) << 1)) << 5; }
+
+__global__ __launch_bounds__(256, 2) void upsample_t_mma_kernel(UpMmaArgs a) {
+  typedef bf16_t T;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lg = lane >> 4;
+  // this lane's output column ow' = li: 0..7 the tile's 8 columns of scale 2, 8..11 scale 4, 12..13 scale 8, 14..15 none
+  const int sid = li < 8 ? 0 : li < 12 ? 1 : li < 14 ? 2 : 3;
+  const int ls = sid + 1, S = 1 << ls, side = HM_T >> ls;
+  const int o = li - (sid == 0 ? 0 : sid == 1 ? 8 : 12);
+  const float inv = sid == 0 ? 0.5f : sid == 1 ? 0.25f : 0.125f;
+  char* const outp = sid == 0 ? a.out[0] : sid == 1 ? a.out[1] : sid == 2 ? a.out[2] : nullptr;
+  const int hs = a.H >> ls, ws = a.W >> ls;
+  const int uoff = UM_HALO - S / 2;      // u = Y - uoff
+  // (every XCD - workgroup ids go round-robin over the 8 of them - walks a contiguous run of jobs: the chunks of a tile
+  // and the overlapping halos of neighbouring tiles meet in one L2)
+  const int per = (a.njobs + 7) >> 3, g8 = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7;
+  auto job_at = [&](int j) -> int {
+    const int job = xcd * per + j;
+    return (j < per && job < a.njobs) ? job : -1;
+  };
+  // staging: vector 3 m + i of this thread is channel vector sv of region pixel 96 m + 32 i + (tid >> 3), which lies
+  // in region row 4 m + sr[i], column sx[i] (96 pixels = 4 rows); slds[i] = its LDS byte address for m = 0
+  const auto rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.g, 0, (int)a.g_bytes, 0x00020000);
+  constexpr unsigned OOB = 0x80000000u;      // (a load there returns zeros)
+  const int sv = tid & 7;
+  int sr[3], sx[3], slds[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int p = 32 * i + (tid >> 3);
+    sr[i] = p / UM_R; sx[i] = p % UM_R;
+    slds[i] = p * UM_PXB + ((sv * 16) ^ um_swz(sx[i]));
+  }
+  const int row_b = a.W * a.C * 2;           // bytes between image rows
+  auto gload = [&](int job, V16 (&val)[UM_NV]) {
+    const int chunk = job % a.chunks;
+    int t = job / a.chunks;
+    const int tx = t % a.tiles_x; t /= a.tiles_x;
+    const int ty = t % a.tiles_y;
+    const int img = t / a.tiles_y;
+    const int ch = chunk * UM_CH + sv * 8;
+    const int Yr = ty * HM_T - UM_HALO, Xr = tx * HM_T - UM_HALO;
+    int off[3];
+    bool xok[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int X = Xr + sx[i];
+      xok[i] = X >= 0 && X < a.W && ch < a.C;
+      off[i] = ((img * a.H + Yr + sr[i]) * a.W + X) * a.C * 2 + ch * 2;      // (used only where the pixel exists)
+    }
+#pragma unroll
+    for (int m = 0; m < UM_NV / 3; ++m)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int Y = Yr + 4 * m + sr[i];
+        const bool ok = xok[i] && Y >= 0 && Y < a.H;
+        val[3 * m + i] = __builtin_amdgcn_raw_buffer_load_b128(rg, ok ? (unsigned)(off[i] + 4 * m * row_b) : OOB, 0, 0);
+      }
+  };
+  // transposing read of a region row: lane (li, lg) addresses pixel 8 * lg + (li >> 2) (and the one 4 further), channels
+  // 4 * (li & 3) .. + 3 of this wave's 16, and receives pixels 8 * lg .. + 7 of channel li. lg = 3 is the K padding:
+  // its weights are zero, and what it reads - the first 8 pixels of the NEXT region row, behind the last row 8 pixels
+  // that are zeroed here once - is finite wherever G is.
+  const int rd = (lg * 8 + (li >> 2)) * UM_PXB + ((wave * 32 + (li & 3) * 8) ^ um_swz(lg * 8 + (li >> 2)));
+  if (tid < 8 * UM_PXB / 16) *(V16*)(lds + UM_R * UM_R * UM_PXB + tid * 16) = v16_zero();
+  // the rows' weights without the border rule, per lane: fB[Y] for the row's first-half footprint, fA[Y] for its
+  // second-half one (zero above the first footprint of the lane's scale)
+  float fB[UM_R], fA[UM_R];
+#pragma unroll
+  for (int Y = 0; Y < UM_R; ++Y) {
+    const int u = Y - uoff;
+    const float f = ((float)(u & (S - 1)) + 0.5f) * inv;
+    fB[Y] = u < 0 ? 0.f : f;
+    fA[Y] = u < 0 ? 0.f : 1.f - f;
+  }
+
+  V16 val[UM_NV];
+  int j = (int)blockIdx.x >> 3;
+  int job = job_at(j);
+  if (job >= 0) gload(job, val);
+  while (job >= 0) {        // (uniform)
+    const int chunk = job % a.chunks;
+    int t = job / a.chunks;
+    const int tx = t % a.tiles_x; t /= a.tiles_x;
+    const int ty = t % a.tiles_y;
+    const int img = t / a.tiles_y;
+    __syncthreads();        // the previous job's reads of the region are done
+#pragma unroll
+    for (int m = 0; m < UM_NV / 3; ++m)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) *(V16*)(lds + slds[i] + m * 96 * UM_PXB) = val[3 * m + i];
+    j += g8;
+    const int next = job_at(j);
+    if (next >= 0) gload(next, val);
+    __syncthreads();
+
+    // B fragment: wx of this lane's output column at region columns 8 * lg .. + 7 (upt_scale's rule along x)
+    const int ow = tx * side + o;
+    float wx[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int rx = 8 * lg + e - (UM_HALO + S * o - S / 2);
+      float w = 0.f;
+      if (rx >= 0 && rx < 2 * S) {
+        w = rx < S ? ((float)rx + 0.5f) * inv : 1.f - ((float)(rx - S) + 0.5f) * inv;
+        if ((ow == 0 && rx < S) || (ow == ws - 1 && rx >= S)) w = 1.f;
+      }
+      wx[e] = (outp != nullptr && ow < ws) ? w : 0.f;
+    }
+    const V16 bw = v16_pack<T>(wx);
+    // rows: the two running sums (aA: second half of its footprint, aB: first half)
+    const bool top = ty == 0;
+    const int lastA = hs - ty * side;      // u >> ls of the rows whose second-half output row is the image's last
+    const int c0 = chunk * UM_CH + wave * 16 + 4 * lg;
+    const bool live = outp != nullptr && ow < ws && c0 < a.C;
+    const int orow = ws * a.C * 2;
+    // aA belongs to tile row ohc, stored at sp; rows 0 .. nrow-1 of the tile exist in the image
+    char* sp = live ? outp + ((((size_t)img * hs + ty * side) * ws + ow) * a.C + c0) * 2 - 2 * (ptrdiff_t)orow : nullptr;
+    const int nrow = live ? min(side, hs - ty * side) : 0;
+    int ohc = -2;
+    // (u is formed inside the job loop: hoisted out of it, the 24 rows' masks and shifted indices of a lane join the
+    // 48 weight registers and the 72 of the next job's loads, and the spills' reloads wait for those loads)
+    int uo = uoff;
+    asm volatile("" : "+v"(uo));
+    float aA[4] = {0.f, 0.f, 0.f, 0.f}, aB[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int Y = 0; Y <= UM_R; ++Y) {
+      const int u = Y - uo;
+      // (the rows at which some scale completes an output row: u a multiple of s - odd Y from 3, Y = 2 mod 4, Y = 0 mod 8)
+      if ((Y >= 3 && (Y - 3) % 2 == 0) || (Y >= 2 && (Y - 2) % 4 == 0) || Y % 8 == 0) {
+        if (u >= 0 && (u & (S - 1)) == 0) {
+          if (ohc >= 0 && ohc < nrow) {
+            const bf16x4 b = {(bf16_t)aA[0], (bf16_t)aA[1], (bf16_t)aA[2], (bf16_t)aA[3]};
+            *(u32x2*)sp = __builtin_bit_cast(u32x2, b);
+          }
+          ++ohc;
+          sp += orow;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) { aA[c] = aB[c]; aB[c] = 0.f; }
+        }
+      }
+      if (Y == UM_R) break;
+      const LDS_AS char* l = (const LDS_AS char*)lds + Y * UM_R * UM_PXB + rd;
+      const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4*)l);
+      const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((LDS_AS bf16x4*)(l + 4 * UM_PXB));
+      const bf16x8 av = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+      const f32x4 tr = mma16<T>(__builtin_bit_cast(V16, av), bw, f32x4{0.f, 0.f, 0.f, 0.f});
+      // the border rule. (u < 0 - above the first footprint - meets neither: in a top tile those region rows lie
+      // outside the image and hold zeros, and u >> ls = -1 is never lastA >= 1)
+      const float wB = (top && u < S) ? 1.f : fB[Y];       // first half of the image's first row: clamped
+      const float wA = (u >> ls) == lastA ? 1.f : fA[Y];   // second half of its last row: clamped
+      aB[0] = fmaf(wB, tr.x, aB[0]); aB[1] = fmaf(wB, tr.y, aB[1]);
+      aB[2] = fmaf(wB, tr.z, aB[2]); aB[3] = fmaf(wB, tr.w, aB[3]);
+      aA[0] = fmaf(wA, tr.x, aA[0]); aA[1] = fmaf(wA, tr.y, aA[1]);
+      aA[2] = fmaf(wA, tr.z, aA[2]); aA[3] = fmaf(wA, tr.w, aA[3]);
+      // (four rows' reads and products in flight at a time: hoisting all 24 rows' reads spills beside the 72 registers
+      // of the next job's loads)
+      if (Y % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+    job = next;
+  }
+}
+
 int mix_cap(int hs, int H) { return (15 * hs) / H + 3; }
 
 }  // namespace
@@ -626,6 +872,8 @@ static int head_launch(HeadMixArgs& a, int dtype, int mode, hipStream_t s) {
   }
   a.sl_off = off;
   off += 4 * 2 * HM_CH * (int)sizeof(float);
+  a.cf_off = off;
+  off += (mode == 0 ? 1 : 5) * HM_CH * (int)sizeof(float);
   const long long tiles = (long long)a.N * a.tiles_y * a.tiles_x;
   if (dtype == HR_F32) {
     HR_REQUIRE(tiles < (1ll << 31), "head_mix: grid");
@@ -723,6 +971,37 @@ int hr_upsample_t_tile(int dtype, const void* g, void* const* outs, const int* h
   const int vec = dtype == HR_F32 ? 4 : 8;
   a.g = (const char*)g; a.ns = nout; a.N = N; a.H = H; a.W = W; a.C = C; a.halo = halo;
   a.tiles_y = (H + HM_T - 1) / HM_T; a.tiles_x = (W + HM_T - 1) / HM_T;
+  // bf16: the matrix-pipe form (one output per scale; HRNET_UPT_MMA=0 under HRNET_MEASURE keeps the form above for A/Bs)
+  const double g_bytes = (double)N * H * W * C * 2.0;
+  bool mma = dtype == HR_BF16 && C % 8 == 0 && g_bytes < 2147483648.0 && hr_knob("HRNET_UPT_MMA", 1) != 0;
+  UpMmaArgs m = {};
+  for (int k = 0; k < nout && mma; ++k) {
+    const int slot = a.sc[k] == 2 ? 0 : a.sc[k] == 4 ? 1 : 2;
+    if (m.out[slot]) mma = false;      // (two outputs of one scale: the form above)
+    m.out[slot] = a.out[k];
+  }
+  if (mma) {
+    m.g = a.g; m.N = N; m.H = H; m.W = W; m.C = C; m.g_bytes = (unsigned)g_bytes;
+    m.tiles_y = a.tiles_y; m.tiles_x = a.tiles_x; m.chunks = (C + UM_CH - 1) / UM_CH;
+    const long long njobs = (long long)N * a.tiles_y * a.tiles_x * m.chunks;
+    if (njobs >= (1ll << 31)) return 1;
+    m.njobs = (int)njobs;
+    static bool attr_set = false;
+    if (!attr_set &&
+        hipFuncSetAttribute((const void*)upsample_t_mma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, UM_LDS) !=
+            hipSuccess) {
+      hr_set_error("upsample_t: hipFuncSetAttribute failed");
+      return HR_E_BADARG;
+    }
+    attr_set = true;
+    // two resident workgroups per CU; fewer jobs than that: one workgroup per job (a multiple of 8: one run per XCD)
+    long long grid = hr_knob("HRNET_UPT_GRID", 512);
+    if (grid > njobs) grid = njobs;
+    if (grid < 1) grid = 1;
+    grid = (grid + 7) / 8 * 8;
+    hipLaunchKernelGGL(upsample_t_mma_kernel, dim3((unsigned)grid), dim3(256), (size_t)UM_LDS, s, m);
+    return 0;
+  }
   a.chunks = (C / vec + 3) / 4;
   const int R = HM_T + 2 * halo;
   const size_t lds = (size_t)R * (R * UT_PXB + 16);
