@@ -30,7 +30,7 @@ int hr_check_launch(const char* what) {
 
 extern "C" const char* hrnet_last_error_string(void) { return g_err; }
 // 2: HR_CONV_I_ROUTE, HR_WGRAD_I_ATOMIC .. HR_WGRAD_I_LD, HrPackEnt.ld, the head / table op kinds of round 3
-extern "C" int hrnet_abi_version(void) { return 2; }
+extern "C" int hrnet_abi_version(void) { return HR_ABI_VERSION; }
 
 static int run_one(const HrOp& op, hipStream_t s, int k) {
   int e;

@@ -16,8 +16,9 @@ import torch
 
 from hipnet import _capi as C
 
-OP_LAYERNORM, OP_LINEAR, OP_ATTENTION, OP_FRAME_MEAN = 0, 1, 2, 3
-ACT_NONE, ACT_GELU = 0, 1
+OP_LAYERNORM, OP_LINEAR, OP_ATTENTION, OP_FRAME_MEAN = (
+    C.VALUES['HR_TF_' + n] for n in ('LAYERNORM', 'LINEAR', 'ATTENTION', 'FRAME_MEAN'))
+ACT_NONE, ACT_GELU = C.VALUES['HR_TF_ACT_NONE'], C.VALUES['HR_TF_ACT_GELU']
 _ACTS = {None: ACT_NONE, 'none': ACT_NONE, 'gelu': ACT_GELU}
 
 

@@ -26,9 +26,10 @@ import torch
 from core.loss import _dev_f32
 from hipnet import _capi as C
 
-METHODS = {'sum': 0, 'max': 1, 'softmax': 2}        # HR_VOL_*; any name beginning with 'conf' is 3
+METHODS = {'sum': C.VALUES['HR_VOL_SUM'], 'max': C.VALUES['HR_VOL_MAX'], 'softmax': C.VALUES['HR_VOL_SOFTMAX']}
+CONF = C.VALUES['HR_VOL_CONF']                       # any name beginning with 'conf'
 MAX_VIEWS = 8
-SPLIT = 32                                          # HR_VOLUME_SPLIT
+SPLIT = C.VALUES['HR_VOLUME_SPLIT']
 
 
 def _method_id(volume_aggregation_method, vol_confidences):
@@ -37,7 +38,7 @@ def _method_id(volume_aggregation_method, vol_confidences):
     if volume_aggregation_method.startswith('conf'):
         if vol_confidences is None:
             raise ValueError("volume_aggregation_method '{}' needs vol_confidences".format(volume_aggregation_method))
-        return 3
+        return CONF
     if volume_aggregation_method not in METHODS:
         raise ValueError('Unknown volume_aggregation_method: {}'.format(volume_aggregation_method))
     return METHODS[volume_aggregation_method]
@@ -67,7 +68,7 @@ class _UnprojectFn(torch.autograd.Function):
         X, Y, Z = coord.shape[1:4]
         gV = gV.contiguous().float()
         dfeat = torch.empty_like(feat)
-        dconf = torch.empty_like(conf) if ctx.method == 3 and ctx.needs_input_grad[1] else None
+        dconf = torch.empty_like(conf) if ctx.method == CONF and ctx.needs_input_grad[1] else None
         C.call('hrnet_unproject_volume_bwd', feat.data_ptr(), proj.data_ptr(), coord.data_ptr(), C.ptr(conf),
                gV.data_ptr(), dfeat.data_ptr(), C.ptr(dconf), ctx.method, B, V, Cn, H, W, X, Y, Z, C.stream_ptr())
         return dfeat, dconf, None, None, None
@@ -93,13 +94,13 @@ def unproject_heatmaps(heatmaps, proj_matricies, coord_volumes, volume_aggregati
         raise ValueError('proj_matricies: expected {}, got {}'.format((B, V, 3, 4), tuple(proj_matricies.shape)))
     if coord_volumes.ndim != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
         raise ValueError('coord_volumes: expected ({}, X, Y, Z, 3), got {}'.format(B, tuple(coord_volumes.shape)))
-    if method == 3 and tuple(vol_confidences.shape) != (B, V, Cn):
+    if method == CONF and tuple(vol_confidences.shape) != (B, V, Cn):
         raise ValueError('vol_confidences: expected {}, got {}'.format((B, V, Cn), tuple(vol_confidences.shape)))
     if not 1 <= V <= MAX_VIEWS:
         raise ValueError('heatmaps: {} views (1..{})'.format(V, MAX_VIEWS))
     _constant(proj_matricies, 'proj_matricies', 'unproject_heatmaps')
     _constant(coord_volumes, 'coord_volumes', 'unproject_heatmaps')
-    conf_in = vol_confidences if method == 3 else None
+    conf_in = vol_confidences if method == CONF else None
     feat = _dev_f32(heatmaps, 'unproject_heatmaps')
     proj = _dev_f32(proj_matricies, 'unproject_heatmaps')
     coord = _dev_f32(coord_volumes, 'unproject_heatmaps')

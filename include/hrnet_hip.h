@@ -10,14 +10,17 @@
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is DEVICE memory owned by the caller
- *     (PyTorch's caching allocator); the library allocates nothing.
+ *     (PyTorch's caching allocator) unless it is marked HR_HOST; the library allocates nothing.
  *   - activations are NHWC; `dtype` selects the storage/arithmetic type of activations and
  *     packed weights: HR_F32 (exact f32 MFMA, f32 accumulate) or HR_BF16 (bf16 MFMA, f32
  *     accumulate). Statistics, BN coefficients, partial sums, losses and master weights
  *     are always f32.
  *   - stream-ordered and re-entrant: kernels are enqueued on `stream`, nothing synchronises.
- *   - return 0 on success, a negative HR_E_* code otherwise; hrnet_last_error_string()
- *     describes the last failure of the calling thread. Nothing throws across the ABI.
+ *   - a function declared `int` returns a status: 0 on success, a negative HR_E_* code otherwise;
+ *     hrnet_last_error_string() describes the last failure of the calling thread. Any other return type
+ *     (hr_value_t, long long, a pointer) is a value. Nothing throws across the ABI.
+ *   - lib/hipnet/_header.py reads this file and the ctypes binding is built from what it finds (prototypes, structs,
+ *     enumerators, integer HR_* macros), so the header keeps to the C that reader knows; it refuses the rest.
  */
 #ifndef HRNET_HIP_H
 #define HRNET_HIP_H
@@ -28,7 +31,11 @@
 extern "C" {
 #endif
 
+#define HR_ABI_VERSION 2 /* hrnet_abi_version() of a library built from this header */
+#define HR_HOST /* on a pointer parameter: host memory the call reads or writes before it returns */
+
 typedef void* hr_stream_t; /* hipStream_t */
+typedef int hr_value_t;    /* a count, flag or mode, not a status */
 
 enum { HR_F32 = 0, HR_BF16 = 1 };
 
@@ -253,20 +260,21 @@ enum { HR_POOL_P_G = 0, HR_POOL_P_MASK, HR_POOL_P_Y0, HR_POOL_P_DZ0, HR_POOL_P_P
 enum { HR_EWJOB_I_BLOCK0 = 16, HR_EWJOB_I_BLOCKS = 17, HR_EWJOB_I_SUM_EPS_BITS = 18 };
 
 const char* hrnet_last_error_string(void);
-int hrnet_abi_version(void);
+hr_value_t hrnet_abi_version(void);
 
 /* Run `n` recorded ops in order on `stream` (one host call per forward / backward pass). */
-int hrnet_program_run(const HrOp* ops, int n, hr_stream_t stream);
+int hrnet_program_run(HR_HOST const HrOp* ops, int n, hr_stream_t stream);
 /* blocks of one job of a HR_OP_EW_TABLE launch (kind = the single op's kind; finalize: N = H = W = 1) */
-int hrnet_ew_table_blocks(int kind, int dtype, int N, int H, int W, int C);
+hr_value_t hrnet_ew_table_blocks(int kind, int dtype, int N, int H, int W, int C);
 /* The same over several streams: op.i[HR_LANE_SLOT] selects streams[lane]; HR_OP_EVENT_RECORD /
  * HR_OP_STREAM_WAIT ops express the dependencies between lanes (independent branches of a
  * HighResolutionModule, weight-gradient work off the critical path). Events come from
  * hrnet_event_create (host-side handles; no device memory). */
-int hrnet_program_run_streams(const HrOp* ops, int n, const hr_stream_t* streams, int nstreams);
+int hrnet_program_run_streams(HR_HOST const HrOp* ops, int n, HR_HOST const hr_stream_t* streams, int nstreams);
 /* Measurement form of the above: a timing event behind every op on its lane; end_ms[k] = completion of op k in
  * ms since the call began on op 0's lane. Synchronises every stream before returning (not for the training loop). */
-int hrnet_program_run_streams_timed(const HrOp* ops, int n, const hr_stream_t* streams, int nstreams, float* end_ms);
+int hrnet_program_run_streams_timed(HR_HOST const HrOp* ops, int n, HR_HOST const hr_stream_t* streams, int nstreams,
+                                    HR_HOST float* end_ms);
 void* hrnet_event_create(void);
 int hrnet_event_destroy(void* event);
 
@@ -294,7 +302,7 @@ int hrnet_conv2d(int dtype, const void* x, const void* w, const float* in_scale,
 /* out[i] = sum_{j<k} coefs[j] * srcs[j][i], f32, k <= 8 (host arrays of k device pointers / k coefficients): the
  * frame differences and the weighted temporal aggregation of pose_hrnet_PoseAggr
  * (lib/models/pose_hrnet_PoseAggr.py:612-640) */
-int hrnet_lincomb_f32(float* out, long long n, int k, const float* const* srcs, const float* coefs,
+int hrnet_lincomb_f32(float* out, long long n, int k, HR_HOST const float* const* srcs, HR_HOST const float* coefs,
                       hr_stream_t stream);
 
 /*
@@ -329,37 +337,38 @@ int hrnet_conv2d_bwdstats(int dtype, const void* x, const void* w, void* y, floa
  * than 16x16 (it serves them correctly but loses inside the training step, so 1 keeps it to 16x16 maps). Returns the
  * previous setting (-1: never decided).
  */
-int hrnet_conv_ring_enable(int on);
-int hrnet_conv_ring_supported(int dtype, int N, int H, int W, int Cin, int Cout);
+hr_value_t hrnet_conv_ring_enable(int on);
+hr_value_t hrnet_conv_ring_supported(int dtype, int N, int H, int W, int Cin, int Cout);
 /* statistics rows hrnet_conv2d_bwdstats leaves for a launch of this shape (hrnet_conv_tiles_bwdstats() for the
  * tile-walking body; the pixel walks of the LDS-ring grid where that serves the launch) */
-int hrnet_conv_rows_bwdstats(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);
+hr_value_t hrnet_conv_rows_bwdstats(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);
 /* kernel family a RECORDED backward-statistics launch of this shape is bound to (HR_CONV_I_ROUTE): 2 = LDS ring,
  * 1 = tile-walking body; the rows buffer above is sized for that family, so the op keeps the decision and a later
  * hrnet_conv_ring_enable() cannot change how many rows the launch writes (it fails instead). 0 = decide at launch. */
-int hrnet_conv_route(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);
+hr_value_t hrnet_conv_route(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride);
 /* hrnet_conv2d_sum on the LDS-ring pipeline for the narrow branch layers (bf16, 3x3, 32 / 64 input channels): off by
  * default (measured slower inside the training step), on = 1; returns the previous setting */
-int hrnet_conv_ring_sum_enable(int on);
+hr_value_t hrnet_conv_ring_sum_enable(int on);
 
 /* name of the kernel instantiation chosen for a shape, as rocprofv3 demangles it (returns length) */
-int hrnet_conv_kernel_name(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride, int upz,
-                           int mode, char* buf, int buflen);
+hr_value_t hrnet_conv_kernel_name(int dtype, int N, int Ho, int Wo, int Cin, int Cout, int ks, int stride, int upz,
+                                  int mode, HR_HOST char* buf, int buflen);
 /* the specialised kernel family a conv launch uses: 0 conv_kernel (everything by run-time flag), 1
  * conv_bs_kernel (backward statistics), 2 conv_fwd_kernel (forward conv feeding a BatchNorm), 3
  * conv_dg_kernel (plain input gradient), 4 conv_fwdb_kernel (forward conv with bias) */
-int hrnet_conv_mode(int bwdstats, int has_bias, int upz, int accumulate, int has_stats, int has_affine,
-                    int in_relu);
-int hrnet_wgrad_kernel_name(int dtype, int Ho, int Wo, int Cout, int Cin, int ks, int stride, char* buf,
-                            int buflen);
+hr_value_t hrnet_conv_mode(int bwdstats, int has_bias, int upz, int accumulate, int has_stats, int has_affine,
+                           int in_relu);
+hr_value_t hrnet_wgrad_kernel_name(int dtype, int Ho, int Wo, int Cout, int Cin, int ks, int stride,
+                                   HR_HOST char* buf, int buflen);
 /* number of per-tile stat rows hrnet_conv2d writes for this shape */
-int hrnet_conv_tiles(int N, int Ho, int Wo, int Cout, int ks, int stride);
+hr_value_t hrnet_conv_tiles(int N, int Ho, int Wo, int Cout, int ks, int stride);
 /* the tile walk of a conv launch: out5 = {tile h, tile w, output-channel block, pixel tiles per workgroup,
  * pixel walks (= statistics rows)}; returns the number of pixel tiles. s2d = the four-parity input gradient
  * of a 3x3 stride-2 conv (upz with hrnet_conv2d_bwdstats or a plain input-gradient launch). */
-int hrnet_conv_tile_walk(int N, int Ho, int Wo, int Cout, int ks, int stride, int bwdstats, int s2d, int* out5);
+hr_value_t hrnet_conv_tile_walk(int N, int Ho, int Wo, int Cout, int ks, int stride, int bwdstats, int s2d,
+                                HR_HOST int* out5);
 /* rows of a hrnet_conv2d_bwdstats launch (its tile choice differs for wide 1x1 outputs) */
-int hrnet_conv_tiles_bwdstats(int N, int Ho, int Wo, int Cout, int ks, int stride);
+hr_value_t hrnet_conv_tiles_bwdstats(int N, int Ho, int Wo, int Cout, int ks, int stride);
 
 /*
  * Weight gradient: slabs[s][Cout][ks*ks][Cin] f32 partial sums over disjoint pixel ranges
@@ -370,11 +379,11 @@ int hrnet_conv2d_wgrad(int dtype, const void* x, const void* dy, const float* in
                        const float* in_shift, float* slabs, int N, int H, int W, int Cin, int Ho,
                        int Wo, int Cout, int ks, int stride, int in_relu, int nsplit,
                        hr_stream_t stream);
-int hrnet_wgrad_splits(int dtype, int N, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
+hr_value_t hrnet_wgrad_splits(int dtype, int N, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
 /* pixel tiles the launch walks in all (a split takes tiles / nsplit of them, grid-strided) */
-int hrnet_wgrad_tiles(int dtype, int N, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
+hr_value_t hrnet_wgrad_tiles(int dtype, int N, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
 /* workgroups per split (a launch runs splits x this many) */
-int hrnet_wgrad_blocks_per_split(int dtype, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
+hr_value_t hrnet_wgrad_blocks_per_split(int dtype, int Ho, int Wo, int Cout, int Cin, int ks, int stride);
 /* slabs -> grad_oihw[Cout_real][Cin_real][ks][ks] f32 (+= if accumulate). Cout/Cin are the
  * padded slab extents; stem: kflat=1 means slab K index is the flattened (tap,ci) of the
  * im2col'ed stem (Cin_real*ks*ks real entries). */
@@ -399,14 +408,15 @@ int hrnet_conv3x3_bwd_fused(int dtype, const void* dz, const void* y, const floa
                             const float* in_scale, const float* in_shift, int in_relu, const void* wT, void* dx,
                             const void* addend, int mask_out, float* rows, const void* bs_y, float* slabs, int N,
                             int H, int W, int Cin, int Cout, hr_stream_t stream);
-int hrnet_bwd_fused_supported(int dtype, int Cin, int Cout);
+hr_value_t hrnet_bwd_fused_supported(int dtype, int Cin, int Cout);
 /*
  * The fused launches can finish the BatchNorm backward of their own output themselves: instead of `coef` (written by
  * a hrnet_bn_bwd_finalize launch in between) they take the partial rows [nrows][2][Cout] the previous launch left
  * - every workgroup sums them in a fixed order (f64) and builds A,B,C itself; the first workgroup also adds
  * dgamma / dbeta. Same arithmetic as hrnet_bn_bwd_finalize, deterministic, one launch and one dependency less per
- * BatchNorm. `ref` is a HOST struct copied into the launch; NULL = use `coef`. Keep nrows * Cout <= 16384
- * (3x3) / 8192 (1x1): every workgroup reads all rows.
+ * BatchNorm. `ref` is a HOST struct copied into the launch; NULL = use `coef`. It is not marked HR_HOST: a recorded
+ * op carries it as an address (HR_BWD_FUSED_P_BNREF), and callers of the direct form pass the address too. Keep
+ * nrows * Cout <= 16384 (3x3) / 8192 (1x1): every workgroup reads all rows.
  */
 typedef struct HrBnBwdRef {
   const float* rows;    /* [nrows][2][Cout]: (sum dz, sum dz*y) partials */
@@ -423,8 +433,8 @@ int hrnet_conv3x3_bwd_fused_bnref(int dtype, const void* dz, const void* y, cons
                                   const void* wT, void* dx, const void* addend, int mask_out, float* rows,
                                   const void* bs_y, float* slabs, int N, int H, int W, int Cin, int Cout,
                                   hr_stream_t stream);
-int hrnet_bwd_fused_splits(int dtype, int N, int H, int W, int Cin, int Cout);
-int hrnet_bwd_fused_kernel_name(int dtype, int Cin, int Cout, char* buf, int buflen);
+hr_value_t hrnet_bwd_fused_splits(int dtype, int N, int H, int W, int Cin, int Cout);
+hr_value_t hrnet_bwd_fused_kernel_name(int dtype, int Cin, int Cout, HR_HOST char* buf, int buflen);
 
 /*
  * The same fused backward for a 1x1 (pointwise) convolution: the conv1 / conv3 / downsample layers of a
@@ -443,10 +453,10 @@ int hrnet_conv1x1_bwd_fused_bnref(int dtype, const void* dz, const void* y, cons
                                   const void* wT, void* dx, const void* addend, int mask_out, float* rows,
                                   const void* bs_y, float* slabs, long long pixels, int Cin, int Cout,
                                   hr_stream_t stream);
-int hrnet_bwd_pw_supported(int dtype, int Cin, int Cout);
-int hrnet_bwd_pw_rows_supported(int dtype, int Cin, int Cout);
-int hrnet_bwd_pw_splits(int dtype, long long pixels, int Cin, int Cout);
-int hrnet_bwd_pw_kernel_name(int dtype, int Cin, int Cout, char* buf, int buflen);
+hr_value_t hrnet_bwd_pw_supported(int dtype, int Cin, int Cout);
+hr_value_t hrnet_bwd_pw_rows_supported(int dtype, int Cin, int Cout);
+hr_value_t hrnet_bwd_pw_splits(int dtype, long long pixels, int Cin, int Cout);
+hr_value_t hrnet_bwd_pw_kernel_name(int dtype, int Cin, int Cout, HR_HOST char* buf, int buflen);
 
 /*
  * Pack f32 OIHW master weights into the kernels' layout.
@@ -470,7 +480,7 @@ typedef struct HrPackEnt {
 } HrPackEnt;
 int hrnet_pack_weights_table(int dtype, const HrPackEnt* table, int n, int total_blocks,
                              hr_stream_t stream);
-int hrnet_pack_blocks(int Cout_pad, int Cin_pad, int ks, int mode);
+hr_value_t hrnet_pack_blocks(int Cout_pad, int Cin_pad, int ks, int mode);
 
 /* hrnet_wgrad_reduce for many convolutions in ONE launch (each layer keeps its own slab region):
  * `table` is a DEVICE array of n entries; entry e covers blocks [block0, block0 +
@@ -545,9 +555,10 @@ typedef struct HrBnEnt {
 int hrnet_bn_finalize_table(const HrBnEnt* table, int n, int total_blocks, hr_stream_t stream);
 /* hrnet_sum_terms with BatchNorm terms given as batch sums: bit t of sums_mode set -> scale[t] = sums[8][2][C],
  * shift[t] = gamma (beta = gamma + C), inv_counts[t] = 1 / (elements per channel of term t) */
-int hrnet_sum_terms_bnref(int dtype, void* out, int N, int Ho, int Wo, int C, int nterms, const void* const* src,
-                          const float* const* scale, const float* const* shift, const int* shifts, const int* relus,
-                          int relu_out, int sums_mode, const float* inv_counts, float eps, hr_stream_t stream);
+int hrnet_sum_terms_bnref(int dtype, void* out, int N, int Ho, int Wo, int C, int nterms,
+                          HR_HOST const void* const* src, HR_HOST const float* const* scale,
+                          HR_HOST const float* const* shift, HR_HOST const int* shifts, HR_HOST const int* relus,
+                          int relu_out, int sums_mode, HR_HOST const float* inv_counts, float eps, hr_stream_t stream);
 
 /*
  * out[N,Ho,Wo,C] = relu_out( sum_{t<nterms} relu_t( src_t[nearest-up by 2^sh_t] * scale_t + shift_t ) )
@@ -555,8 +566,9 @@ int hrnet_sum_terms_bnref(int dtype, void* out, int N, int Ho, int Wo, int C, in
  * (pose_hrnet.py:257-264, :206). scale_t may be NULL (identity term).
  */
 int hrnet_sum_terms(int dtype, void* out, int N, int Ho, int Wo, int C, int nterms,
-                    const void* const* src, const float* const* scale, const float* const* shift,
-                    const int* shifts, const int* relus, int relu_out, hr_stream_t stream);
+                    HR_HOST const void* const* src, HR_HOST const float* const* scale,
+                    HR_HOST const float* const* shift, HR_HOST const int* shifts, HR_HOST const int* relus,
+                    int relu_out, hr_stream_t stream);
 
 /*
  * Backward of one term of hrnet_sum_terms / of a BN(+ReLU) that feeds a conv:
@@ -577,7 +589,7 @@ int hrnet_grad_term2(int dtype, void* dst, void* dst2, const void* g, const void
 int hrnet_bn_bwd_reduce(int dtype, float* partials, const void* g, const void* mask_out,
                         const void* y, const float* scale, const float* shift, int N, int H, int W,
                         int C, int sh, int inner_relu, hr_stream_t stream);
-int hrnet_reduce_blocks(int N, int H, int W, int C);
+hr_value_t hrnet_reduce_blocks(int N, int H, int W, int C);
 /* dgamma/dbeta (+=) and coef[3][C]: A = gamma*invstd, B = -gamma*invstd^2*mean(dz*xhat)/... */
 int hrnet_bn_bwd_finalize(const float* partials, int blocks, int C, float count,
                           const float* gamma, const float* save_mean, const float* save_invstd,
@@ -590,12 +602,12 @@ int hrnet_bn_bwd_finalize(const float* partials, int blocks, int C, float count,
  * align_corners=1: F.interpolate(..., align_corners=True) of pose_hrnet_softmax.py:499-503).
  * Branch j has spatial size (H>>j, W>>j) ... given explicitly. nbr <= 4.
  */
-int hrnet_bilinear_cat(int dtype, void* cat, const void* const* xs, const int* hs, const int* ws,
-                       const int* cs, int nbr, int N, int H, int W, int align_corners,
+int hrnet_bilinear_cat(int dtype, void* cat, HR_HOST const void* const* xs, HR_HOST const int* hs,
+                       HR_HOST const int* ws, HR_HOST const int* cs, int nbr, int N, int H, int W, int align_corners,
                        hr_stream_t stream);
 /* dxs[j] (+)= bilinear^T(dcat[..., slice_j]) (gather form, deterministic) */
-int hrnet_bilinear_cat_bwd(int dtype, const void* dcat, void* const* dxs, const int* hs,
-                           const int* ws, const int* cs, int nbr, int N, int H, int W,
+int hrnet_bilinear_cat_bwd(int dtype, const void* dcat, HR_HOST void* const* dxs, HR_HOST const int* hs,
+                           HR_HOST const int* ws, HR_HOST const int* cs, int nbr, int N, int H, int W,
                            int align_corners, int accumulate, hr_stream_t stream);
 
 /*
@@ -611,10 +623,10 @@ int hrnet_bilinear_cat_bwd(int dtype, const void* dcat, void* const* dxs, const 
  * w0: hrnet_pack_weights layout [Cout][C0].
  */
 int hrnet_head_mix(int dtype, const void* x0, const void* w0, const float* bias, void* y, float* stats, int rows_mode,
-                   const void* const* ts, const int* hs, const int* ws, int nup, int N, int H, int W, int C0, int Cout,
-                   int align_corners, hr_stream_t stream);
-int hrnet_head_mix_rows(int N, int H, int W);
-int hrnet_head_mix_supported(int dtype, int C0, int Cout);
+                   HR_HOST const void* const* ts, HR_HOST const int* hs, HR_HOST const int* ws, int nup, int N, int H,
+                   int W, int C0, int Cout, int align_corners, hr_stream_t stream);
+hr_value_t hrnet_head_mix_rows(int N, int H, int W);
+hr_value_t hrnet_head_mix_supported(int dtype, int C0, int Cout);
 /* Backward of the 1x1 layer BEHIND the head's BatchNorm + ReLU (last_layer[3] of pose_hrnet.py:341-346) fused with that
  * BatchNorm's backward (autograd of nn.Conv2d / nn.ReLU / nn.BatchNorm2d): dz = wT dY (K = the layer's padded output
  * channels) is formed per pixel tile and masked by [bn_scale*y + bn_shift > 0] (inner_relu), never stored.
@@ -627,8 +639,9 @@ int hrnet_head_bwd(int dtype, int mode, const void* dy, const void* wT, const vo
 /* outs[k][N,hs[k],ws[k],C] = bilinear^T(G[N,H,W,C]) over ALL channels, k < nout <= 3: the gradients of t_j above
  * (autograd of F.upsample, pose_hrnet.py:561-563). Deterministic. Integer scales 2 / 4 / 8 with align_corners=0 take
  * ONE pass over G for all outputs (LDS-staged tiles); anything else (or streamed=1) a separable streamed walk per output. */
-int hrnet_upsample_bilinear_t(int dtype, const void* g, void* const* outs, const int* hs, const int* ws, int nout,
-                              int N, int H, int W, int C, int align_corners, int streamed, hr_stream_t stream);
+int hrnet_upsample_bilinear_t(int dtype, const void* g, HR_HOST void* const* outs, HR_HOST const int* hs,
+                              HR_HOST const int* ws, int nout, int N, int H, int W, int C, int align_corners,
+                              int streamed, hr_stream_t stream);
 
 /* stem: NCHW f32 image -> im2col rows [N,Ho,Wo,Kpad] (k = (r*3+s)*C + c), 3x3 stride 2 pad 1
  * (conv1, pose_hrnet.py:283-284,512). */
@@ -682,7 +695,7 @@ int hrnet_decode_argmax(const float* hms, float* preds, float* maxvals, int BK, 
 int hrnet_gaussian_targets(const float* pose2d, const float* visibility, float* heatmaps, int BK, int H,
                            int W, float sigma, hr_stream_t stream);
 int hrnet_normalize_u8(const unsigned char* img_nhwc, float* out_nchw, int N, int H, int W,
-                       const float* mean3, const float* std3, hr_stream_t stream);
+                       HR_HOST const float* mean3, HR_HOST const float* std3, hr_stream_t stream);
 
 /*
  * Input step of tools/inference.py (reference tools/inference.py:117-121: cv2.resize to IMAGE_SIZE, then
@@ -696,7 +709,7 @@ int hrnet_normalize_u8(const unsigned char* img_nhwc, float* out_nchw, int N, in
  * pitch < 3*W, is not read: its output plane is NaN. mean3/std3 are HOST arrays of 3 floats.
  */
 int hrnet_resize_normalize_u8(const unsigned char* src, int64_t src_bytes, const int64_t* slots, int n,
-                              float* out_nchw, int Ho, int Wo, const float* mean3, const float* std3,
+                              float* out_nchw, int Ho, int Wo, HR_HOST const float* mean3, HR_HOST const float* std3,
                               int bgr, hr_stream_t stream);
 
 /*
@@ -712,8 +725,8 @@ int hrnet_resize_normalize_u8(const unsigned char* src, int64_t src_bytes, const
  * mean3/std3 are HOST arrays of 3 floats.
  */
 int hrnet_affine_warp_normalize_u8(const unsigned char* src, int64_t src_bytes, const int64_t* slots,
-                                   const float* inv_mats, int n, float* out_nchw, int Ho, int Wo, const float* mean3,
-                                   const float* std3, hr_stream_t stream);
+                                   const float* inv_mats, int n, float* out_nchw, int Ho, int Wo,
+                                   HR_HOST const float* mean3, HR_HOST const float* std3, hr_stream_t stream);
 
 /*
  * Multi-view DLT triangulation of tools/evaluate_3D.py (reference tools/evaluate_3D.py:178-190,270-301,
@@ -870,7 +883,7 @@ int hrnet_volumetric_ce_loss_bwd(const float* p, const float* validity, const in
  *   relu != 0, THEN + add[n,.,.,.,c] if add != NULL - the decoder's x = upsample(x) + skip_x (v2v.py:123-136).
  * conv3d_supported: 1 if conv3d serves (dtype, Cin, Cout, ks), else 0. Pure host query, no error code.
  */
-int hrnet_conv3d_supported(int dtype, int Cin, int Cout, int ks);
+hr_value_t hrnet_conv3d_supported(int dtype, int Cin, int Cout, int ks);
 int hrnet_conv3d(int dtype, const void* x, const void* w_packed, const float* scale, const float* shift,
                  const void* res, void* y, int N, int D, int H, int W, int Cin, int Cout, int ks, int relu,
                  hr_stream_t stream);
@@ -925,7 +938,7 @@ int hrnet_deconv3d_k2s2(int dtype, const void* x, const void* w_packed, const fl
  *   x [N,D,H,W,Cin], dz [N,2D,2H,2W,Cout]. The voxels are split over workgroups into nsplit partial sums in scratch,
  *   which a second launch adds in split order. accumulate != 0 adds to dw, else dw is overwritten.
  */
-int hrnet_bn3d_parts(long long rows);
+hr_value_t hrnet_bn3d_parts(long long rows);
 int hrnet_bn3d_stats(int dtype, const void* z, const float* gamma, const float* beta, float* scratch, float* mean,
                      float* invstd, float* scale, float* shift, float* running_mean, float* running_var,
                      long long* num_batches_tracked, int N, int D, int H, int W, int C, int Creal, float momentum,
@@ -943,7 +956,7 @@ int hrnet_pack_weights3d_dgrad(int dtype, const float* w, void* out, int Cout, i
 int hrnet_deconv3d_k2s2_dgrad(int dtype, const void* dz, const void* w_packed, void* dx, int N, int D, int H, int W,
                               int Cin, int Cout, int accumulate, hr_stream_t stream);
 int hrnet_conv3d_wgrad_scratch(int dtype, int N, int D, int H, int W, int Cin, int Cout, int ks, int deconv,
-                               long long* bytes, int* nsplit, long long* split_voxels);
+                               HR_HOST long long* bytes, HR_HOST int* nsplit, HR_HOST long long* split_voxels);
 int hrnet_conv3d_wgrad(int dtype, const void* x, const void* dz, void* scratch, long long scratch_bytes, float* dw, int N,
                        int D, int H, int W, int Cin, int Cout, int Cin_real, int Cout_real, int ks, int deconv,
                        int accumulate, hr_stream_t stream);
@@ -961,10 +974,10 @@ int hrnet_conv3d_wgrad(int dtype, const void* x, const void* dz, void* scratch, 
  * No atomics: a call is bit-reproducible. Any P, Cin and Cout within the limits; 16-byte accesses are used when
  * P % 4 == 0 (Cin % 4 == 0 for w) and the pointers are 16-byte aligned.
  */
-int hrnet_pointwise_nchw_supported(int dtype, int Cin, int Cout);
+hr_value_t hrnet_pointwise_nchw_supported(int dtype, int Cin, int Cout);
 int hrnet_pointwise_nchw(int dtype, const float* x, const float* w, const float* bias, float* y, int N, int Cin,
                          int Cout, long long P, hr_stream_t stream);
-int hrnet_pointwise_nchw_parts(int N, long long P);
+hr_value_t hrnet_pointwise_nchw_parts(int N, long long P);
 int hrnet_pointwise_nchw_bwd(int dtype, const float* x, const float* w, const float* dy, float* dx, float* dw, float* db,
                              float* scratch, long long scratch_floats, int N, int Cin, int Cout, long long P,
                              hr_stream_t stream);
@@ -984,11 +997,12 @@ int hrnet_pointwise_nchw_bwd(int dtype, const float* x, const float* w, const fl
  * used when P % 4 == 0 and every pointer is 16-byte aligned; any other P takes element-wise loads in the same kernels.
  * A weight element is read once per forward and once per dH pass while B * K <= 192; each dW element is written once.
  */
-int hrnet_view_fusion_supported(int dtype, int V, int P);
-int hrnet_view_fusion(int dtype, const float* H, const void* const* W, float* F, int B, int V, int K, int P,
+hr_value_t hrnet_view_fusion_supported(int dtype, int V, int P);
+int hrnet_view_fusion(int dtype, const float* H, HR_HOST const void* const* W, float* F, int B, int V, int K, int P,
                       float w_self, float w_other, hr_stream_t stream);
-int hrnet_view_fusion_bwd(int dtype, const float* H, const void* const* W, const float* dF, float* dH, void* const* dW,
-                          int B, int V, int K, int P, float w_self, float w_other, hr_stream_t stream);
+int hrnet_view_fusion_bwd(int dtype, const float* H, HR_HOST const void* const* W, const float* dF, float* dH,
+                          HR_HOST void* const* dW, int B, int V, int K, int P, float w_self, float w_other,
+                          hr_stream_t stream);
 
 /*
  * Transformer kernels of pose_hrnet_transformer, the reference's PoseFormer head (csrc/transformer.hip; reference
@@ -1024,7 +1038,7 @@ int hrnet_view_fusion_bwd(int dtype, const float* H, const void* const* W, const
  */
 enum { HR_TF_LAYERNORM = 0, HR_TF_LINEAR = 1, HR_TF_ATTENTION = 2, HR_TF_FRAME_MEAN = 3 };
 enum { HR_TF_ACT_NONE = 0, HR_TF_ACT_GELU = 1 };
-int hrnet_tf_supported(int op, int a, int b);
+hr_value_t hrnet_tf_supported(int op, int a, int b);
 long long hrnet_tf_layernorm_scratch(long long rows, int C);
 int hrnet_tf_layernorm(const float* x, const float* gamma, const float* beta, float* y, long long rows, int C, float eps,
                        hr_stream_t stream);
@@ -1126,7 +1140,7 @@ int hrnet_deform_conv_forward(const float* input, const float* offset, const flo
                               const float* bias, float* output, int B, int C, int H, int W, int Co,
                               int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                               int groups, int deformable_groups, hr_stream_t stream);
-int hrnet_deform_conv_wgrad_blocks(int B, int Ho, int Wo);
+hr_value_t hrnet_deform_conv_wgrad_blocks(int B, int Ho, int Wo);
 int hrnet_deform_conv_backward(const float* input, const float* offset, const float* weight,
                                const float* grad_output, float* grad_input, float* grad_offset,
                                float* grad_weight, float* grad_bias, float* scratch, int B, int C,
