@@ -24,7 +24,7 @@ from config import cfg, update_config
 from core.function import train, validate
 from core.loss import BoneLengthLoss, HeatmapLoss, JointAngleLoss, JointsMSELoss
 from dataset.build import make_dataloader
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax, pose_hrnet_transformer  # noqa: F401  (dispatched by name below)
+from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401  (dispatched by name below)
 from utils.utils import create_logger, get_optimizer, save_checkpoint
 
 
@@ -59,9 +59,17 @@ def build_criterion(cfg, device=None):
     return criterion if device is None else {k: m.to(device) for k, m in criterion.items()}
 
 
+def check_config(cfg):
+    """what this tool refuses of a config, before any device work"""
+    if cfg.MODEL.NAME == 'swin_transformer':
+        raise ValueError('MODEL.NAME swin_transformer: {} (no backward kernels, no stochastic depth); evaluation works: '
+                         'tools/evaluate_2D.py and tools/inference.py run it'.format(swin_transformer.NOT_BUILT))
+
+
 def main():
     args = parse_args()
     update_config(cfg, args)
+    check_config(cfg)
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))

@@ -1061,6 +1061,39 @@ int hrnet_tf_add_rows(const float* x, const float* pos, float* y, long long rows
                       hr_stream_t stream);
 
 /*
+ * Swin kernels of swin_transformer, the reference's SwinPose (csrc/swin.hip; reference lib/models/swin_transformer.py).
+ * Forward only. Everything is f32, row-major, 64-bit element offsets, no float atomics: a call is bit-reproducible. Every
+ * entry refuses what it has no kernel for (HR_E_BADARG) before it launches anything. The query takes (op, a, b):
+ * HR_SWIN_ATTENTION (ws, hd): 1 <= ws * ws <= 64, 1 <= hd <= 128; HR_SWIN_MERGE (C, unused): 1 <= 4 C <= 65536;
+ * HR_SWIN_EMBED (Cin, p): 1 <= Cin * p * p <= 65536.
+ *
+ * Window attention straight from token order (:237-269, :317-368, :491-510): qkv (B, H * W, 3, heads, hd) as the qkv linear
+ * wrote it for the UNPADDED tokens, qkv_bias (3 * heads * hd), bias_table ((2 ws - 1)^2, heads), out (B, H * W, heads * hd).
+ * Hp, Wp = H, W rounded up to multiples of ws. A token of the padded border has q = k = v = the qkv bias (the reference
+ * pads after norm1 and before the qkv linear); it takes part as key and query, its output row is dropped. With shift > 0
+ * token (i, j) of the shifted grid is padded-grid token ((i + shift) mod Hp, (j + shift) mod Wp), and -100 is added to the
+ * logit of two tokens whose region ids 3 * band(i, Hp) + band(j, Wp) differ (bands [0, Hp - ws), [Hp - ws, Hp - shift),
+ * [Hp - shift, Hp)). logit = scale * q.k + bias_table[rel(n, m), head], rel = the reference's relative_position_index.
+ * One workgroup per (image, window, head); q, k, v, logits and probabilities live in LDS; both products run on
+ * mfma_f32_16x16x4f32 with the ws * ws tokens padded to 64 (a padding lane's probability is exactly 0).
+ *
+ * Patch merging + LayerNorm (:390-415): x (B, H, W, C) -> y (B * ceil(H / 2) * ceil(W / 2), 4 C), channel blocks
+ * [x(0,0), x(1,0), x(0,1), x(1,1)] (row parity fastest), zeros beyond an odd H or W, then LayerNorm(4 C) with f64 row
+ * sums. gamma and beta both NULL: the gathered rows are stored as they are (no LayerNorm).
+ *
+ * Patch rows (:550-559): NCHW x (B, Cin, H, W) -> rows (B * ceil(H / p) * ceil(W / p), Cin * p * p), column
+ * c * p * p + kh * p + kw, zeros right of W and below H: a Conv2d(Cin, E, p, stride p) weight (E, Cin, p, p) is then the
+ * (E, Cin * p * p) matrix of a plain linear launch, read in place.
+ */
+enum { HR_SWIN_ATTENTION = 0, HR_SWIN_MERGE = 1, HR_SWIN_EMBED = 2 };
+hr_value_t hrnet_swin_supported(int op, int a, int b);
+int hrnet_swin_attention(const float* qkv, const float* qkv_bias, const float* bias_table, float* out, int B, int H,
+                         int W, int heads, int hd, int ws, int shift, float scale, hr_stream_t stream);
+int hrnet_swin_merge_ln(const float* x, const float* gamma, const float* beta, float* y, int B, int H, int W, int C,
+                        float eps, hr_stream_t stream);
+int hrnet_swin_patch_rows(const float* x, float* rows, int B, int Cin, int H, int W, int p, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with

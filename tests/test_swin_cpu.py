@@ -1,0 +1,263 @@
+"""Host side of swin_transformer (SwinPose): tests/swin_ref.py against the fixture of the reference's own run, the model's
+state dict for both backbone settings, every refusal, the C entry points' argument checks, the yaml, tools/train.py's refusal
+and the bench tool's cost model. No GPU."""
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import swin_ref as R
+
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'hrnet-hand-pose-estimation_amd')
+YAML = os.path.join(PKG, 'experiments', 'RHD', 'RHD_HRNet_w32_SwinTransformer_v3.yaml')
+SMALL = ['MODEL.IMAGE_SIZE', '[64, 64]', 'MODEL.HEATMAP_SIZE', '[16, 16]', 'MODEL.EMB_DIM', '[48]', 'MODEL.DEPTHS',
+         '[2, 2, 2, 2]']
+SWIN_NAMES = ['hrnet_swin_supported', 'hrnet_swin_attention', 'hrnet_swin_merge_ln', 'hrnet_swin_patch_rows']
+
+
+def _cfg(opts=()):
+    from config import get_cfg_defaults
+    cfg = get_cfg_defaults()
+    cfg.merge_from_file(YAML)
+    cfg.merge_from_list(list(opts))
+    return cfg
+
+
+@pytest.fixture(scope='module')
+def golden(golden_dir):
+    return np.load(os.path.join(golden_dir, 'swin.npz'))
+
+
+def _table(golden, tag):
+    return [(str(k), tuple(int(v) for v in s[:int(np.count_nonzero(s))]))
+            for k, s in zip(golden[tag + '/keys'], golden[tag + '/shapes'])]
+
+
+@pytest.mark.parametrize('tag,case', [('a', R.CASE_A), ('b', R.CASE_B)])
+def test_restatement_against_the_fixture(golden, tag, case):
+    """float64: 1e-10 of max|.| against the reference's float64 run; float32: of the order of the stored error of the
+    float32 restatement (what the GPU bounds are built from) and of the reference's own float32 run"""
+    seed = int(golden['seed'])
+    x = R.inputs(case, seed)
+    assert np.array_equal(x, golden[tag + '/x'].astype(np.float64))
+    y64 = golden[tag + '/y64']
+    assert R.rel(R.run(case, torch.float64, seed), y64) <= 1e-10
+    e32 = float(golden[tag + '/e32'])
+    assert R.rel(R.run(case, torch.float32, seed), y64) <= 2 * e32 <= 5e-6
+    assert R.rel(golden[tag + '/y32'], y64) <= 5e-6                       # the reference's own float32 run
+    if tag == 'a':
+        assert y64.shape == (2, 21, 16, 16) and np.abs(y64.sum(axis=(2, 3)) - 1).max() <= 1e-12
+    else:
+        assert y64.shape == (1, 2, 768)
+    want = _table(golden, tag)
+    assert want == (R.head_keys(case) if tag == 'a' else R.head_keys(case)[1:])
+
+
+def test_filled_state_is_not_trivial():
+    state = R.fill_state_dict(R.head_keys(R.CASE_A))
+    for k, v in state.items():
+        if k.endswith(('.bias', 'relative_position_bias_table')):
+            assert np.abs(v).min() > 0, k
+        if k.endswith('running_var'):
+            assert v.min() >= 0.5 and np.abs(v - 1).min() > 0, k
+    gammas = np.concatenate([state['decoder.{}.weight'.format(i)] for i in (2, 6, 10, 14)])
+    assert 0.15 < (gammas < 0).mean() < 0.5
+    assert np.array_equal(state['swinTransformer.layers.0.blocks.1.attn.relative_position_index'],
+                          R.rel_index(7).numpy())
+    # rel_index, element by element: the offset (dr, dc) in -2 .. 2 as a digit pair in base 2 ws - 1
+    idx = R.rel_index(3)
+    for n in range(9):
+        for m in range(9):
+            assert int(idx[n, m]) == (n // 3 - m // 3 + 2) * 5 + (n % 3 - m % 3 + 2)
+    assert int(R.rel_index(7).min()) == 0 and int(R.rel_index(7).max()) == 168
+
+
+def test_window_attention_is_what_the_block_computes():
+    """attention_from_qkv (bias rows for the padded tokens) is the reference's pad-then-linear route: the restatement's
+    window_attention on normalised tokens h equals attention_from_qkv on qkv = h W^T + b, so what the device tests compare
+    the attention kernel with is the reference's semantics."""
+    g = torch.Generator().manual_seed(5)
+    H, W, heads, hd, ws = 8, 5, 3, 4, 7
+    C = heads * hd
+    h = torch.randn(2, H * W, C, generator=g, dtype=torch.float64)
+    w, b = torch.randn(3 * C, C, generator=g, dtype=torch.float64), torch.randn(3 * C, generator=g, dtype=torch.float64)
+    table = torch.randn((2 * ws - 1) ** 2, heads, generator=g, dtype=torch.float64)
+    for shift in (0, 3):
+        one = R.window_attention(h, H, W, w, b, table, heads, ws, shift)
+        two = R.attention_from_qkv(h @ w.t() + b, b, table, H, W, heads, ws, shift, hd ** -0.5)
+        assert R.rel(two.numpy(), one.numpy()) <= 1e-13
+
+
+@pytest.mark.parametrize('tag,backbone', [('full', 'pose_hrnet_softmax'), ('full_nb', '')])
+def test_state_dict_keys_shapes_and_order(golden, tag, backbone):
+    from models import swin_transformer
+    want = _table(golden, tag)
+    assert want == R.head_keys(R.FULL if backbone else R.FULL_NO_BACKBONE) and len(want) == (396 if backbone else 378)
+    model = swin_transformer.get_pose_net(_cfg(['MODEL.BACKBONE_NAME', backbone]), is_train=True)
+    sd = model.state_dict()
+    keys = list(sd)
+    assert [(k, tuple(sd[k].shape)) for k in keys if not k.startswith('backbone.')] == want
+    assert keys[0] == 'trainable_temp'
+    if backbone:
+        first = keys.index('swinTransformer.patch_embed.proj.weight')
+        assert all(k.startswith('backbone.') for k in keys[1:first]) and first > 1
+        assert not any(k.startswith('backbone.') for k in keys[first:])
+        trains = {k for k, p in model.named_parameters() if p.requires_grad}
+        assert trains == {k for k, _ in model.named_parameters()
+                          if not k.startswith('backbone.') or k.startswith('backbone.stage4.')}
+    else:
+        assert not hasattr(model, 'backbone') and len(model.decoder) == 2 * 4 + 1
+    assert sum(int(np.prod(s)) for _, s in want) == (52802252 if backbone else 52402362)
+    st = model.swinTransformer
+    assert [b.shift_size for b in st.layers[2].blocks] == [0, 3] * 9 and st.layers[3].downsample is None
+    assert [l.blocks[0].attn.num_heads for l in st.layers] == [3, 6, 12, 24]
+    assert torch.equal(st.layers[0].blocks[0].attn.relative_position_index, R.rel_index(7))
+    for holder in (st, st.layers[0], st.layers[0].blocks[0], st.layers[0].blocks[0].attn, st.patch_embed):
+        with pytest.raises(NotImplementedError):
+            holder(torch.zeros(1, 49, 96))
+    # a reference-shaped checkpoint loads strictly
+    ckpt = {k: (v if k.startswith('backbone.') else torch.zeros_like(v)) for k, v in sd.items()}
+    swin_transformer.get_pose_net(_cfg(['MODEL.BACKBONE_NAME', backbone]), is_train=False).load_state_dict(ckpt, strict=True)
+
+
+def test_backbone_checkpoint_is_loaded_non_strictly(tmp_path):
+    from models import pose_hrnet_softmax, swin_transformer
+    torch.manual_seed(1)
+    src = pose_hrnet_softmax.get_pose_net(_cfg(SMALL), is_train=False)
+    state = {'module.' + k: v + 0.25 for k, v in src.state_dict().items() if k.startswith(('conv1.', 'stage4.'))}
+    state['module.not_a_key'] = torch.zeros(1)
+    path = str(tmp_path / 'backbone.pth.tar')
+    torch.save({'state_dict': state, 'epoch': 3}, path)
+    m = swin_transformer.get_pose_net(_cfg(SMALL + ['MODEL.BACKBONE_MODEL_PATH', path]), is_train=True)
+    assert torch.equal(m.backbone.conv1.weight, src.conv1.weight + 0.25)
+
+
+def test_refusals():
+    from hipnet import swin as S
+    from models import swin_transformer as M
+    for opts, match in ((['MODEL.FF_TYPE', 'conv'], 'FF_TYPE'),
+                        (['MODEL.ABSOLUTE_POSITION_ENCODING', 'True'], 'ABSOLUTE_POSITION_ENCODING'),
+                        (['MODEL.EMB_DIM', '[100]'], 'EMB_DIM'),
+                        (['MODEL.IMAGE_SIZE', '[64, 48]'], 'IMAGE_SIZE'),
+                        (['MODEL.HEATMAP_SIZE', '[16, 12]'], 'HEATMAP_SIZE'),
+                        (['MODEL.BACKBONE_NAME', 'pose_hrnet'], 'BACKBONE_NAME'),
+                        (['MODEL.PATCH_SIZE', '8'], 'PATCH_SIZE')):
+        with pytest.raises(ValueError, match=match):
+            M.get_pose_net(_cfg(SMALL + opts), is_train=False)
+    model = M.get_pose_net(_cfg(SMALL + ['MODEL.BACKBONE_NAME', '']), is_train=False)
+    x = torch.zeros(1, 3, 64, 64)
+    with pytest.raises(NotImplementedError, match='training of swin_transformer is not built'):
+        model.train()(x)
+    model.eval()
+    with pytest.raises(NotImplementedError, match='training of swin_transformer is not built'):
+        model(x)                                                         # eval mode, a gradient required
+    with torch.no_grad():
+        with pytest.raises(ValueError, match='HIP-device'):
+            model(x)
+        with pytest.raises(ValueError, match='HIP-device'):
+            model.head_forward(x)
+    c = torch.zeros(1, 4, 24)
+    for call in (lambda: S.window_attention(c, c[0, 0], torch.zeros(169, 2), 2, 2, 2, 7, 0, 1.0),
+                 lambda: S.merge_ln(c, 2, 2), lambda: S.patch_rows(torch.zeros(1, 3, 8, 8), 2),
+                 lambda: S.conv_transpose_pack(torch.zeros(8, 16, 3, 3)), lambda: S.conv_pack(torch.zeros(16, 8, 1, 1)),
+                 lambda: S.conv_nhwc(torch.zeros(1, 2, 2, 8), torch.zeros(128), 16, 1),
+                 lambda: S.heatmap_softmax(torch.zeros(1, 2, 2, 32), 21, torch.ones(()))):
+        with pytest.raises(ValueError, match='HIP-device'):
+            call()
+
+
+def test_abi_names_are_exported_and_refuse_by_argument_check():
+    from hipnet import _capi as C
+    lib = C.lib()
+    for name in SWIN_NAMES:
+        assert name in C.EXPORTED and hasattr(lib, name), name
+    A, M, E = (C.VALUES['HR_SWIN_' + n] for n in ('ATTENTION', 'MERGE', 'EMBED'))
+    sup = lambda *a: C.call('hrnet_swin_supported', *a)
+    assert sup(A, 7, 32) == 1 and sup(A, 8, 128) == 1 and sup(A, 9, 32) == 0 and sup(A, 7, 129) == 0 and sup(A, 0, 8) == 0
+    assert sup(M, 768, 0) == 1 and sup(M, 16385, 0) == 0 and sup(E, 480, 2) == 1 and sup(E, 3, 0) == 0 and sup(9, 1, 1) == 0
+    p = 4096                                                           # never dereferenced: every call below is refused
+    attn = lambda **k: C.call('hrnet_swin_attention', k.get('qkv', p), p, p, k.get('out', 2 * p), k.get('B', 1), 8, 8, 3,
+                              k.get('hd', 32), k.get('ws', 7), k.get('shift', 0), 1.0, None)
+    for kw, match in ((dict(ws=9), 'ws = 9'), (dict(hd=129), 'hd = 129'), (dict(shift=7), 'shift = 7'),
+                      (dict(shift=-1), 'shift = -1'), (dict(B=0), 'B = 0'), (dict(qkv=None), 'null pointer'),
+                      (dict(out=p), 'aliases')):
+        with pytest.raises(RuntimeError, match=match):
+            attn(**kw)
+    with pytest.raises(RuntimeError, match='C = 0'):
+        C.call('hrnet_swin_merge_ln', p, p, p, 2 * p, 1, 2, 2, 0, 1e-5, None)
+    with pytest.raises(RuntimeError, match='come together'):
+        C.call('hrnet_swin_merge_ln', p, p, None, 2 * p, 1, 2, 2, 8, 1e-5, None)
+    with pytest.raises(RuntimeError, match='eps'):
+        C.call('hrnet_swin_merge_ln', p, p, p, 2 * p, 1, 2, 2, 8, 0.0, None)
+    with pytest.raises(RuntimeError, match='p = 0'):
+        C.call('hrnet_swin_patch_rows', p, 2 * p, 1, 3, 8, 8, 0, None)
+    with pytest.raises(RuntimeError, match='null pointer'):
+        C.call('hrnet_swin_patch_rows', None, 2 * p, 1, 3, 8, 8, 2, None)
+    assert "'swin.hip'" in open(os.path.join(PKG, 'build.py')).read()
+
+
+def test_yaml_values():
+    cfg = _cfg()
+    M = cfg.MODEL
+    assert M.NAME == 'swin_transformer' and M.BACKBONE_NAME == 'pose_hrnet_softmax' and M.BACKBONE_MODEL_PATH == ''
+    assert M.PATCH_SIZE == 2 and list(M.DEPTHS) == [2, 2, 18, 2] and M.FF_TYPE == 'mlp' and list(M.EMB_DIM) == [96]
+    assert M.ABSOLUTE_POSITION_ENCODING is False and M.HEATMAP_SOFTMAX is True and M.TRAINABLE_SOFTMAX is True
+    assert list(M.IMAGE_SIZE) == [256, 256] and list(M.HEATMAP_SIZE) == [64, 64] and M.INIT_WEIGHTS is False
+    assert cfg.LOSS.WITH_POSE2D_LOSS and not cfg.LOSS.WITH_HEATMAP_LOSS and cfg.TRAIN.LR == 6e-5 and cfg.TRAIN.WD == 0.01
+    from models import swin_transformer as S
+    assert S.emb_dim(_cfg(['MODEL.EMB_DIM', '[48]'])) == 48 and S.decoder_steps(cfg) == (64, 480, 4)
+    for tool in ('train.py', 'evaluate_2D.py', 'inference.py'):
+        src = open(os.path.join(PKG, 'tools', tool)).read()
+        line = next(l for l in src.splitlines() if l.startswith('from models import'))
+        assert 'swin_transformer' in [t.strip() for t in line.split('import', 1)[1].split('#')[0].split(',')]
+
+
+def test_train_refuses_swin_transformer():
+    sys.path.insert(0, os.path.join(PKG, 'tools'))
+    try:
+        spec = importlib.util.spec_from_file_location('swin_train_tool', os.path.join(PKG, 'tools', 'train.py'))
+        tool = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(tool)
+    finally:
+        sys.path.remove(os.path.join(PKG, 'tools'))
+    with pytest.raises(ValueError, match='swin_transformer.*is not built.*evaluation works'):
+        tool.check_config(_cfg())
+    tool.check_config(_cfg(['MODEL.NAME', 'pose_hrnet_softmax']))
+    r = subprocess.run([sys.executable, os.path.join('tools', 'train.py'), '--cfg', YAML], cwd=PKG, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and 'training of swin_transformer is not built' in r.stderr and \
+        'evaluation works' in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_counts_only():
+    r = subprocess.run([sys.executable, os.path.join('tools', 'bench_swin.py'), '--counts-only'], cwd=PKG,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [json.loads(l) for l in r.stdout.strip().splitlines()]
+    assert [row['B'] for row in rows] == [1, 32] and all('times' not in row for row in rows)
+    c = rows[0]['counts']
+    assert c['launches_per_block'] == 7 and c['blocks'] == 24
+    st = c['stages']
+    # by hand for the v3 yaml: 3 for the embedding; 7 per block and 2 per merge; the last norm; 2 per decoder step, the
+    # final 1x1, the layout change and the softmax
+    assert [st[k]['launches'] for k in ('embed', 'stage0', 'stage1', 'stage2', 'stage3', 'norm', 'decoder')] == \
+        [3, 2 * 7 + 2, 2 * 7 + 2, 18 * 7 + 2, 2 * 7, 1, 4 * 2 + 3]
+    assert c['total']['launches'] == 24 * 7 + 3 * 2 + 3 + 1 + 11 == 189
+    # weights read once: every float entry of the state dict but norm0 - norm2 (not computed), plus the qkv bias a second
+    # time (the attention kernel reads it for the padded tokens), the folded (scale, shift) of the decoder in place of
+    # the 1x1 bias and the four BatchNorm vectors, and the final convolution padded to 32 outputs
+    keys = R.head_keys(R.FULL)
+    floats = sum(int(np.prod(s)) for k, s in keys if not k.endswith(('relative_position_index', 'num_batches_tracked'))
+                 and not k.startswith(('swinTransformer.norm0', 'swinTransformer.norm1', 'swinTransformer.norm2')))
+    qkv_bias = sum(int(np.prod(s)) for k, s in keys if k.endswith('qkv.bias'))
+    folded = sum(2 * s[0] - 5 * s[0] for k, s in keys if k.startswith('decoder.') and k.endswith('running_var'))
+    pad = (32 - 21) * (48 + 1)
+    assert c['total']['weight_bytes'] == 4 * (floats + qkv_bias + folded + pad)
+    assert rows[1]['counts']['total']['weight_bytes'] == c['total']['weight_bytes']
+    assert rows[1]['counts']['total']['activation_bytes'] == 32 * c['total']['activation_bytes']
+    assert 30 < c['total']['floor_us'] < 60

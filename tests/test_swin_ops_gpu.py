@@ -1,0 +1,180 @@
+"""The Swin kernels of csrc/swin.hip through hipnet.swin on the GPU against the float64 restatement of tests/swin_ref.py
+(which pads, rolls, partitions and masks as the reference does): window attention from token order, the two gathers with
+their LayerNorm, and one decoder step on the zero-stuffed form of the convolution entry.
+
+err = max|dev - ref64| / max|ref64| must stay within swin_ref.bound(e_ref) = 4 * e_ref + 2 * 2^-24, e_ref being the same
+measure of the restatement run in float32 on the CPU. The gathers alone are exact."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import swin_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def _check(label, dev, r64, r32, bad):
+    dev = dev.double().cpu().numpy()
+    r64, r32 = r64.numpy(), r32.double().numpy()
+    assert dev.shape == r64.shape and np.isfinite(dev).all(), label
+    err, e_ref = R.rel(dev, r64), R.rel(r32, r64)
+    print('{}: err {:.3g} e_ref {:.3g} bound {:.3g}'.format(label, err, e_ref, R.bound(e_ref)))
+    if not err <= R.bound(e_ref):
+        bad.append((label, err, e_ref, R.bound(e_ref)))
+
+
+def _attn_inputs(B, H, W, heads, hd, ws, seed):
+    """float32-valued float64 tensors: qkv (B, H W, 3 C), a non-zero qkv bias and bias table"""
+    g = torch.Generator().manual_seed(seed)
+    C = heads * hd
+    f = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32).double()
+    return f(B, H * W, 3 * C), 0.5 * f(3 * C) + 0.25, 0.5 * f((2 * ws - 1) ** 2, heads)
+
+
+def _attn_device(qkv, bias, table, H, W, heads, ws, shift, scale):
+    from hipnet import swin as S
+    out = S.window_attention(qkv.float().cuda(), bias.float().cuda(), table.float().cuda(), H, W, heads, ws, shift, scale)
+    torch.cuda.synchronize()
+    return out
+
+
+# (H, W), ws, shifts, (heads, hd) pairs
+ATTENTION_CASES = [
+    ((4, 4), 7, (0, 3), ((3, 16), (3, 32))),              # one padded window
+    ((7, 7), 7, (0, 3), ((3, 16), (3, 32))),              # exact fit, no padding
+    ((8, 8), 7, (0, 3), ((3, 16), (3, 32), (1, 1))),      # 2x2 windows, 6 padded rows and columns
+    ((11, 7), 7, (0, 3), ((3, 16), (3, 32))),             # two windows in a column
+    ((11, 7), 3, (0, 1), ((3, 16),)),                     # ws = 3: 4x3 windows of 9 tokens
+    ((1, 1), 7, (0, 3), ((3, 16), (3, 32))),
+    ((5, 9), 7, (0, 3), ((3, 16), (3, 32))),
+    ((9, 6), 7, (0, 3), ((2, 48), (1, 128))),             # hd beyond one staged chunk of 32 channels: 2 and 4 chunks
+]
+
+
+@pytest.mark.parametrize('HW,ws,shifts,shapes', ATTENTION_CASES)
+def test_window_attention_against_the_restatement(HW, ws, shifts, shapes):
+    """every (shift, heads x hd, B in (1, 3)) of the row; each run twice, the bits must be equal.
+    MI355X, err / e_ref / bound: 9.3e-08 .. 6.2e-07 / 7.8e-08 .. 6.6e-07 / 4.3e-07 .. 2.8e-06 over the 64 combinations; the
+    closest to its bound is 11x7, shift 0, hd 16, B = 3 at 0.44 of it (6.18e-07 / 3.18e-07 / 1.39e-06); hd 128 (four staged
+    chunks) gives 5.3e-07 / 4.7e-07 / 2.0e-06."""
+    H, W = HW
+    bad = []
+    for heads, hd in shapes:
+        for shift in shifts:
+            for B in (1, 3):
+                qkv, bias, table = _attn_inputs(B, H, W, heads, hd, ws, seed=1000 * H + 10 * W + shift + B)
+                scale = hd ** -0.5
+                r64 = R.attention_from_qkv(qkv, bias, table, H, W, heads, ws, shift, scale)
+                r32 = R.attention_from_qkv(qkv.float(), bias.float(), table.float(), H, W, heads, ws, shift, scale)
+                a = _attn_device(qkv, bias, table, H, W, heads, ws, shift, scale)
+                b = _attn_device(qkv, bias, table, H, W, heads, ws, shift, scale)
+                assert torch.equal(a, b), 'two runs differ'
+                _check('{}x{} ws {} shift {} heads {} hd {} B {}'.format(H, W, ws, shift, heads, hd, B), a, r64, r32, bad)
+    assert not bad, bad
+
+
+def test_window_attention_nan_stays_in_its_window():
+    """8x8 tokens, shift 3, B = 2: a NaN token at (0, 0) of image 0 lands in the last shifted window, next to padded
+    tokens and across three mask regions. Exactly the rows the float32 restatement makes NaN are NaN (-100 is no
+    -inf: the mask does not stop it inside the window), and every other row keeps the bits of the clean run."""
+    H = W = 8
+    heads, hd, ws, shift = 3, 16, 7, 3
+    qkv, bias, table = _attn_inputs(2, H, W, heads, hd, ws, seed=77)
+    clean = _attn_device(qkv, bias, table, H, W, heads, ws, shift, 0.25)
+    dirty = qkv.clone()
+    dirty[0, 0, :] = float('nan')
+    out = _attn_device(dirty, bias, table, H, W, heads, ws, shift, 0.25)
+    ref = R.attention_from_qkv(dirty.float(), bias.float(), table.float(), H, W, heads, ws, shift, 0.25)
+    nan_dev, nan_ref = torch.isnan(out).cpu(), torch.isnan(ref)
+    assert torch.equal(nan_dev, nan_ref)
+    rows = nan_ref.all(dim=2)
+    assert int(rows[0].sum()) == 9 and int(rows[1].sum()) == 0 and bool((nan_ref.any(dim=2) == rows).all())
+    assert torch.equal(out.cpu()[~nan_dev], clean.cpu()[~nan_dev])
+
+
+@pytest.mark.parametrize('H,W', [(8, 8), (5, 3), (1, 1)])
+def test_merge_gather_and_layernorm(H, W):
+    """MI355X: the gather is exact; after LayerNorm err / e_ref / bound 4.7e-08 / 1.2e-07 / 5.8e-07 (8x8),
+    3.2e-08 / 7.9e-08 / 4.4e-07 (5x3), 3.8e-08 / 1.2e-07 / 6.1e-07 (1x1): the f64 row sums leave the output rounding"""
+    from hipnet import swin as S
+    g = torch.Generator().manual_seed(H * 10 + W)
+    B, C = 2, 48
+    x = torch.randn(B, H * W, C, generator=g, dtype=torch.float32)
+    w = (torch.rand(4 * C, generator=g) + 0.5).double()
+    b = (0.2 * torch.randn(4 * C, generator=g)).double()
+    gathered = S.merge_ln(x.cuda(), H, W)
+    assert torch.equal(gathered.cpu(), R.merge_gather(x, H, W))          # exact
+    dev = S.merge_ln(x.cuda(), H, W, w.float().cuda(), b.float().cuda(), 1e-5)
+    r64 = R.layer_norm(R.merge_gather(x.double(), H, W), w, b)
+    r32 = R.layer_norm(R.merge_gather(x, H, W), w.float(), b.float())
+    bad = []
+    _check('merge {}x{}'.format(H, W), dev, r64, r32, bad)
+    assert not bad, bad
+    assert tuple(dev.shape) == (B, ((H + 1) // 2) * ((W + 1) // 2), 4 * C)
+
+
+@pytest.mark.parametrize('Cin,H,W,p,E', [(3, 41, 25, 4, 96), (480, 16, 16, 2, 48)])
+def test_patch_rows_linear_and_layernorm(Cin, H, W, p, E):
+    """MI355X: the rows are exact; after the linear layer and LayerNorm err / e_ref / bound 1.0e-07 / 2.1e-07 / 9.4e-07
+    (3 x 41 x 25, p 4) and 5.8e-07 / 3.3e-07 / 1.4e-06 (480 x 16 x 16, p 2, a sum over 1920 inputs)"""
+    from hipnet import swin as S
+    from hipnet import transformer as T
+    g = torch.Generator().manual_seed(Cin + p)
+    B = 2
+    x = torch.randn(B, Cin, H, W, generator=g, dtype=torch.float32)
+    wt = (torch.randn(E, Cin, p, p, generator=g) / (Cin * p * p) ** 0.5).double()
+    bs, lw, lb = (0.1 * torch.randn(E, generator=g)).double(), (torch.rand(E, generator=g) + 0.5).double(), \
+        (0.2 * torch.randn(E, generator=g)).double()
+    rows, Hp, Wp = S.patch_rows(x.cuda(), p)
+    want, Hr, Wr = R.embed_rows(x, p)
+    assert (Hp, Wp) == (Hr, Wr) == ((H + p - 1) // p, (W + p - 1) // p)
+    assert torch.equal(rows.cpu(), want)                                   # exact
+    dev = T.layer_norm(T.linear(rows, wt.float().cuda().reshape(E, -1), bs.float().cuda()), lw.float().cuda(),
+                       lb.float().cuda(), 1e-5)
+    # the matrix route is the convolution: the padded Conv2d of the reference gives the same rows
+    conv = F.conv2d(F.pad(x.double(), (0, (p - W % p) % p, 0, (p - H % p) % p)), wt, bs, stride=p)
+    r64 = R.layer_norm(conv.flatten(2).transpose(1, 2).reshape(B * Hp * Wp, E), lw, lb)
+    r32 = R.layer_norm(want @ wt.float().reshape(E, -1).t() + bs.float(), lw.float(), lb.float())
+    bad = []
+    _check('embed {}x{}x{} p {}'.format(Cin, H, W, p), dev, r64, r32, bad)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize('size,cin', [(1, 96), (4, 96), (1, 768), (4, 768)])
+def test_decoder_step_against_conv_transpose2d(size, cin):
+    """ConvTranspose2d(cin, cin / 2, 3, 2, 1, 1) + bias, Conv2d 1x1 + bias, eval BatchNorm with negative gammas, ReLU
+    against torch.nn.functional in float64: the zero-stuffed convolution with the mode-1 packed weight is the transposed
+    convolution, and the folded (scale, shift) + ReLU is applied by the next launch's load (an identity 1x1 here).
+    MI355X, err / e_ref / bound: 1x1 96 -> 48 1.2e-07 / 1.7e-07 / 8.0e-07, 4x4 96 -> 48 2.7e-07 / 2.7e-07 / 1.2e-06,
+    1x1 768 -> 384 9.0e-07 / 4.9e-07 / 2.1e-06, 4x4 768 -> 384 9.9e-07 / 6.9e-07 / 2.9e-06."""
+    from hipnet import swin as S
+    g = torch.Generator().manual_seed(size * 1000 + cin)
+    B, cout = 2, cin // 2
+    f = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32).double()
+    x = f(B, cin, size, size)
+    wT, bT = f(cin, cout, 3, 3) / (cin * 2.25) ** 0.5, 0.1 * f(cout) + 0.05
+    w1, b1 = f(cout, cout, 1, 1) / cout ** 0.5, 0.1 * f(cout) + 0.05
+    gamma = (torch.rand(cout, generator=g).double() + 0.5) * torch.where(torch.arange(cout) % 3 == 0, -1.0, 1.0).double()
+    beta, mean, var = 0.2 * f(cout), 0.3 * f(cout), torch.rand(cout, generator=g).double() * 1.5 + 0.5
+
+    def ref(dt):
+        c = lambda t: t.to(dt)
+        y = F.conv_transpose2d(c(x), c(wT), c(bT), stride=2, padding=1, output_padding=1)
+        y = F.conv2d(y, c(w1), c(b1))
+        return torch.relu(F.batch_norm(y, c(mean), c(var), c(gamma), c(beta), False, 0.1, 1e-5))
+
+    r64, r32 = ref(torch.float64), ref(torch.float32)
+    assert float((r64 == 0).double().mean()) > 0.2                      # the ReLU does cut
+    d = lambda t: t.float().cuda()
+    scale = gamma / torch.sqrt(var + 1e-5)
+    shift = (b1 - mean) * scale + beta
+    y = S.conv_nhwc(d(x).permute(0, 2, 3, 1).contiguous(), S.conv_transpose_pack(d(wT)), cout, 3, up=True, bias=d(bT))
+    y = S.conv_nhwc(y, S.conv_pack(d(w1)), cout, 1)
+    eye = torch.eye(cout, dtype=torch.float32, device='cuda').reshape(cout, cout, 1, 1)
+    y = S.conv_nhwc(y, S.conv_pack(eye), cout, 1, in_scale=d(scale), in_shift=d(shift), in_relu=True)
+    torch.cuda.synchronize()
+    assert tuple(y.shape) == (B, 2 * size, 2 * size, cout)
+    bad = []
+    _check('decoder step {}x{} {} -> {}'.format(size, size, cin, cout), y.permute(0, 3, 1, 2), r64, r32, bad)
+    assert not bad, bad
