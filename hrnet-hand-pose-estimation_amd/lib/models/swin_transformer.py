@@ -1,6 +1,7 @@
 """SwinPose, MODEL.NAME `swin_transformer` (reference lib/models/swin_transformer.py:729-837): a Swin transformer over the
 480-channel feature map of pose_hrnet_softmax (MODEL.BACKBONE_NAME 'pose_hrnet_softmax') or over the bare image
-(BACKBONE_NAME ''), a decoder of transposed convolutions and a spatial softmax. Inference only.
+(BACKBONE_NAME ''), a decoder of transposed convolutions and a spatial softmax. Inference by default; SwinPose(config,
+trainable=True) also trains (the last paragraph).
 
 forward(x): x (B, 3, H, W)
   1. backbone -> features (B, 480, h, w) (slot 1 of pose_hrnet_softmax's output), or x itself                    :817-818
@@ -37,14 +38,25 @@ Refused in forward: CPU tensors (ValueError); training mode, and eval mode with 
 the backward kernels and stochastic depth are not built - run model.eval() under torch.no_grad()).
 
 MODEL.EMB_DIM may be an int, as the reference's yamls write it, or a one-element list, as the default is.
+
+Training is opt-in: SwinPose(config, trainable=True, drop_path_rate=0.2) - get_pose_net(cfg, is_train, trainable=True) -
+runs its training-mode forward on hipnet.swin_train and hipnet.transformer under autograd: the backbone in training mode
+through its autograd anchor (the gradient enters on inter_feat and reaches stage4, the rest is frozen), the patch embedding,
+the blocks with stochastic depth (block k has rate linspace(0, rate, sum(DEPTHS))[k]; each of its two branches draws a
+per-sample keep flag and is scaled by flag / keep_prob; forward and head_forward also take the flags explicitly), patch
+merging as gather, LayerNorm, linear, norm3, and the decoder on batch statistics with every activation materialised. Eval
+mode under no_grad is the inference path above, on the running statistics that training left. Without trainable=True
+nothing changes: training mode and eval mode with a gradient stay refused. WORLD_SIZE > 1 is refused.
 """
 import logging
 import math
+import os
 
 import torch
 import torch.nn as nn
 
 from hipnet import swin as S
+from hipnet import swin_train as ST
 from hipnet import transformer as T
 
 logger = logging.getLogger(__name__)
@@ -52,6 +64,7 @@ logger = logging.getLogger(__name__)
 NUM_HEADS = (3, 6, 12, 24)
 WINDOW = 7
 MLP_RATIO = 4.
+DROP_PATH_RATE = 0.2          # SwinTransformer's default: SwinPose does not pass it (:765-773)
 NOT_BUILT = 'training of swin_transformer is not built'
 
 
@@ -91,9 +104,10 @@ class WindowAttention(nn.Module):
 
 
 class SwinTransformerBlock(nn.Module):
-    def __init__(self, dim, num_heads, window_size, shift_size):
+    def __init__(self, dim, num_heads, window_size, shift_size, drop_path=0.):
         super(SwinTransformerBlock, self).__init__()
         self.dim, self.num_heads, self.window_size, self.shift_size = dim, num_heads, window_size, shift_size
+        self.drop_path = float(drop_path)
         self.norm1 = nn.LayerNorm(dim)
         self.attn = WindowAttention(dim, window_size, num_heads)
         self.norm2 = nn.LayerNorm(dim)
@@ -113,6 +127,18 @@ class SwinTransformerBlock(nn.Module):
         h = T.linear(h, f.fc1.weight, f.fc1.bias, act='gelu')
         return T.linear(h, f.fc2.weight, f.fc2.bias, residual=x)
 
+    def run_train(self, x, H, W, scale_a, scale_m):
+        """the same on the autograd ops; scale_a / scale_m: one stochastic-depth factor per ROW (B * H * W), or None"""
+        a, f = self.attn, self.feed_forward
+        h = T.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        h = T.linear(h, a.qkv.weight, a.qkv.bias)
+        h = ST.window_attention(h, a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.window_size,
+                                self.shift_size, a.scale)
+        x = T.linear(h, a.proj.weight, a.proj.bias, residual=x, row_scale=scale_a)
+        h = T.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        h = T.linear(h, f.fc1.weight, f.fc1.bias, act='gelu')
+        return T.linear(h, f.fc2.weight, f.fc2.bias, residual=x, row_scale=scale_m)
+
 
 class PatchMerging(nn.Module):
     def __init__(self, dim):
@@ -127,13 +153,20 @@ class PatchMerging(nn.Module):
         """x (B, H * W, dim) -> (B, ceil(H / 2) * ceil(W / 2), 2 dim): 2 launches"""
         return T.linear(S.merge_ln(x, H, W, self.norm.weight, self.norm.bias, self.norm.eps), self.reduction.weight)
 
+    def run_train(self, x, H, W):
+        """3 launches: the gather alone, the LayerNorm with its own backward, the linear layer"""
+        h = T.layer_norm(ST.merge_gather(x, H, W), self.norm.weight, self.norm.bias, self.norm.eps)
+        return T.linear(h, self.reduction.weight)
+
 
 class BasicLayer(nn.Module):
-    def __init__(self, dim, depth, num_heads, window_size, downsample):
+    def __init__(self, dim, depth, num_heads, window_size, downsample, drop_path=None):
         super(BasicLayer, self).__init__()
         self.window_size, self.shift_size, self.depth = window_size, window_size // 2, depth
         self.blocks = nn.ModuleList([SwinTransformerBlock(dim, num_heads, window_size,
-                                                          0 if i % 2 == 0 else window_size // 2) for i in range(depth)])
+                                                          0 if i % 2 == 0 else window_size // 2,
+                                                          0. if drop_path is None else drop_path[i])
+                                     for i in range(depth)])
         self.downsample = PatchMerging(dim) if downsample else None
 
     forward = _unused('BasicLayer')
@@ -155,15 +188,23 @@ class PatchEmbed(nn.Module):
         t = T.layer_norm(t, self.norm.weight, self.norm.bias, self.norm.eps)
         return t.reshape(x.shape[0], Hp * Wp, self.embed_dim), Hp, Wp
 
+    def run_train(self, x):
+        rows, Hp, Wp = ST.patch_rows(x, self.patch_size)
+        t = T.linear(rows, self.proj.weight.reshape(self.embed_dim, -1), self.proj.bias)
+        t = T.layer_norm(t, self.norm.weight, self.norm.bias, self.norm.eps)
+        return t.reshape(x.shape[0], Hp * Wp, self.embed_dim), Hp, Wp
+
 
 class SwinTransformer(nn.Module):
-    def __init__(self, patch_size, in_chans, embed_dim, depths):
+    def __init__(self, patch_size, in_chans, embed_dim, depths, drop_path_rate=0.):
         super(SwinTransformer, self).__init__()
         self.num_layers, self.embed_dim = len(depths), embed_dim
         self.patch_embed = PatchEmbed(patch_size, in_chans, embed_dim)
         self.pos_drop = nn.Dropout(p=0.)
+        dpr = [v.item() for v in torch.linspace(0, drop_path_rate, sum(depths))]   # the rate of block k (:640)
         self.layers = nn.ModuleList([
-            BasicLayer(embed_dim * 2 ** i, depths[i], NUM_HEADS[i], WINDOW, downsample=i < len(depths) - 1)
+            BasicLayer(embed_dim * 2 ** i, depths[i], NUM_HEADS[i], WINDOW, downsample=i < len(depths) - 1,
+                       drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])])
             for i in range(len(depths))])
         self.num_features = [embed_dim * 2 ** i for i in range(len(depths))]
         for i in range(len(depths)):
@@ -179,6 +220,29 @@ class SwinTransformer(nn.Module):
                 x = blk.run(x, H, W)
             if layer.downsample is not None:
                 x = layer.downsample.run(x, H, W)
+                H, W = (H + 1) // 2, (W + 1) // 2
+        last = getattr(self, 'norm{}'.format(self.num_layers - 1))
+        return T.layer_norm(x, last.weight, last.bias, last.eps), H, W
+
+    def blocks(self):
+        return [blk for layer in self.layers for blk in layer.blocks]
+
+    def run_train(self, x, flags):
+        """run() on the autograd ops; flags: None, or two per-sample keep-flag tensors (B,) per block, attention branch
+        first. A branch is scaled by flag / keep_prob (timm's DropPath); a block of rate 0 passes no row scale."""
+        B = x.shape[0]
+        x, H, W = self.patch_embed.run_train(x)
+        k = 0
+        for layer in self.layers:
+            for blk in layer.blocks:
+                sa = sm = None
+                if flags is not None and blk.drop_path > 0.:
+                    keep = 1.0 - blk.drop_path
+                    sa, sm = ((flags[2 * k + t].float() / keep).repeat_interleave(H * W).contiguous() for t in range(2))
+                x = blk.run_train(x, H, W, sa, sm)
+                k += 1
+            if layer.downsample is not None:
+                x = layer.downsample.run_train(x, H, W)
                 H, W = (H + 1) // 2, (W + 1) // 2
         last = getattr(self, 'norm{}'.format(self.num_layers - 1))
         return T.layer_norm(x, last.weight, last.bias, last.eps), H, W
@@ -240,10 +304,18 @@ def check_config(config):
 
 
 class SwinPose(nn.Module):
-    def __init__(self, config):
+    autograd_grads = True      # a trainable model's gradients are autograd .grad tensors (utils.get_optimizer)
+
+    def __init__(self, config, trainable=False, drop_path_rate=DROP_PATH_RATE):
         super(SwinPose, self).__init__()
         check_config(config)
         M = config.MODEL
+        self.trainable = bool(trainable)
+        if self.trainable and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise ValueError('SwinPose(trainable=True): WORLD_SIZE = {}: data-parallel training of swin_transformer is '
+                             'not built'.format(os.environ['WORLD_SIZE']))
+        if not 0. <= float(drop_path_rate) < 1.:
+            raise ValueError('drop_path_rate = {}: expected 0 <= rate < 1'.format(drop_path_rate))
         # own parameters precede the sub-modules in a state dict, as the reference's lists them
         self.trainable_temp = nn.Parameter(torch.tensor(1.0), requires_grad=bool(M.TRAINABLE_SOFTMAX))
         size, in_channel, steps = decoder_steps(config)
@@ -263,7 +335,8 @@ class SwinPose(nn.Module):
                 p.requires_grad = True
         e = emb_dim(config)
         self.num_joints = int(config.DATASET.NUM_JOINTS)
-        self.swinTransformer = SwinTransformer(int(M.PATCH_SIZE), in_channel, e, [int(d) for d in M.DEPTHS])
+        self.swinTransformer = SwinTransformer(int(M.PATCH_SIZE), in_channel, e, [int(d) for d in M.DEPTHS],
+                                               float(drop_path_rate) if self.trainable else 0.)
         expand = 2 ** (len(M.DEPTHS) - 1)
         decoder = []
         for i in range(steps):
@@ -321,28 +394,68 @@ class SwinPose(nn.Module):
 
     # ---- the model -----------------------------------------------------------------------------------------------
     def _refuse(self, x):
-        if self.training:
+        if self.training and not self.trainable:
             raise NotImplementedError('SwinPose: {} (the window-attention backward and stochastic depth are the next '
                                       'step): call .eval() and run under torch.no_grad()'.format(NOT_BUILT))
-        if torch.is_grad_enabled() and (getattr(x, 'requires_grad', False) or
-                                        any(p.requires_grad for p in self.parameters())):
+        if not self.training and torch.is_grad_enabled() and (getattr(x, 'requires_grad', False) or
+                                                              any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError('SwinPose: eval mode with a gradient required is refused - {}: run under '
                                       'torch.no_grad()'.format(NOT_BUILT))
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise ValueError('SwinPose: expected HIP-device tensors (there is no CPU path in this build)')
 
-    def head_forward(self, features):
-        """features (B, Cin, H, W) NCHW on the device -> heat maps: everything after the backbone"""
+    # ---- training (trainable=True) -------------------------------------------------------------------------------
+    def draw_drop_flags(self, B, device):
+        """two keep-flag tensors (B,) per block, attention branch first, drawn on the device from torch's generator"""
+        return [torch.empty(B, dtype=torch.float32, device=device).bernoulli_(1.0 - blk.drop_path)
+                for blk in self.swinTransformer.blocks() for _ in range(2)]
+
+    def decoder_train(self, x, H, W):
+        """decoder_forward in training mode: every step's activation is materialised, the BatchNorms run on batch
+        statistics and update their running ones, the packed weights are rebuilt from the parameters every call"""
+        from models.pose_hrnet_softmax import _SpatialSoftmax
+        mods = list(self.decoder)
+        y = x.reshape(x.shape[0], H, W, x.shape[2])
+        for i in range(0, len(mods) - 1, 4):
+            y = ST.decoder_step(y, mods[i], mods[i + 1], mods[i + 2])
+        self._plan = None                 # the running statistics were written through their pointers, not their version
+        y = ST.to_nchw(ST.decoder_final(y, mods[-1]), self.num_joints)
+        return _SpatialSoftmax.apply(y, self.trainable_temp)
+
+    def _check_flags(self, drop_flags, B):
+        n = 2 * len(self.swinTransformer.blocks())
+        drop_flags = list(drop_flags)
+        if len(drop_flags) != n or any(int(f.numel()) != B for f in drop_flags):
+            raise ValueError('drop_flags: {} tensors of sizes {}: expected {} of size {}'.format(
+                len(drop_flags), sorted({int(f.numel()) for f in drop_flags}), n, B))
+        return drop_flags
+
+    def head_forward(self, features, drop_flags=None):
+        """features (B, Cin, H, W) NCHW on the device -> heat maps: everything after the backbone. In training mode of a
+        trainable model drop_flags are the per-sample keep flags of draw_drop_flags (None: drawn here)"""
         self._refuse(features)
         pe = self.swinTransformer.patch_embed
         if features.ndim != 4 or features.shape[1] != pe.in_chans:
             raise ValueError('features {}: expected (B, {}, H, W)'.format(tuple(features.shape), pe.in_chans))
+        if self.training:
+            B = features.shape[0]
+            flags = self.draw_drop_flags(B, features.device) if drop_flags is None else self._check_flags(drop_flags, B)
+            x, H, W = self.swinTransformer.run_train(features.float(), flags)
+            return self.decoder_train(x, H, W)
+        if drop_flags is not None:
+            raise ValueError('drop_flags are for training mode')
         with torch.no_grad():
             x, H, W = self.swinTransformer.run(features.float())
             return self.decoder_forward(x, H, W)
 
-    def forward(self, x):
+    def forward(self, x, drop_flags=None):
         self._refuse(x)
+        if self.training:
+            if hasattr(self, 'backbone'):
+                # the backbone runs in training mode through its autograd anchor; the gradient enters on inter_feat and
+                # reaches stage4 only (the rest is frozen)
+                x = self.backbone(x)[1]
+            return self.head_forward(x, drop_flags), self.trainable_temp
         with torch.no_grad():
             if hasattr(self, 'backbone'):
                 x = self.backbone(x)[1]

@@ -4,6 +4,7 @@ PATCH_SIZE 2, EMB_DIM 96, DEPTHS 2 / 2 / 18 / 2 - against the same head built fr
 
     python tools/bench_swin.py [--batches 1 32] [--repeats 20] [--warmup 3]
     python tools/bench_swin.py --counts-only          (no device: launches and bytes per stage)
+    python tools/bench_swin.py --train [--counts-only]   (the head's training step: forward + backward)
 
 `counts(B)` is the cost model: per stage (embed, stage0 .. stage3 with their patch merging, norm, decoder) the launches of
 one eval forward, the bytes of weights read and of activations read and written, and the floor those bytes give at the
@@ -14,6 +15,12 @@ reverse; F.conv_transpose2d, F.conv2d, F.batch_norm) from torch ops on the model
 same inputs, eval mode under no_grad, timed with device events after a warm-up, alternating with the HIP path; medians
 with the spread (min .. max) over the repeats, for the whole head and per stage. Without a HIP device the timing mode
 fails: there is no fallback.
+
+--train times one training step of the head, forward + backward (hipnet.swin_train and hipnet.transformer under autograd,
+SwinPose(trainable=True, drop_path_rate=0) in training mode: batch-statistic BatchNorm, every activation materialised)
+against the same head from torch ops with autograd on the same parameters, alternating, medians of --repeats after
+--warmup, and appends the spread to profiles/swin_train_times.txt. `train_counts(B)` is its cost model: kernel launches
+of the forward and of the backward per stage, and the bytes they move. No ratio is promised.
 """
 import argparse
 import json
@@ -69,6 +76,64 @@ def counts(B, shape=SHAPE):
     total = {k: sum(s[k] for s in stages.values()) for k in ('launches', 'weight_bytes', 'activation_bytes')}
     total['floor_us'] = 1e6 * (total['weight_bytes'] + total['activation_bytes']) / HBM_BYTES_PER_S
     return {'launches_per_block': 7, 'blocks': sum(shape['depths']), 'stages': stages, 'total': total}
+
+
+def train_counts(B, shape=SHAPE):
+    """launches (forward, backward) and bytes of one training step of the head, per stage and in total. Launches are the
+    kernels inside the C entries: LayerNorm backward 3 (dx, column partials, their sum), linear backward 2 (dx; dW with
+    db), attention backward 2 (the window kernel, the partial-row sum), BatchNorm statistics 3, apply 1, backward 3, weight
+    gradient 2 (slabs, reduce), bias gradient 2, packing 1. torch's own launches (the gradient accumulation where a tensor
+    feeds two consumers: 3 per block; the zero-padded copies of the decoder's vectors) are listed apart."""
+    stages = {}
+
+    def add(name, fwd, bwd, weights, acts, torch_ops=0):
+        s = stages.setdefault(name, {'forward_launches': 0, 'backward_launches': 0, 'torch_launches': 0,
+                                     'weight_bytes': 0, 'activation_bytes': 0})
+        s['forward_launches'] += fwd
+        s['backward_launches'] += bwd
+        s['torch_launches'] += torch_ops
+        s['weight_bytes'] += 4 * weights
+        s['activation_bytes'] += 4 * acts
+
+    e, p, cin = shape['emb'], shape['patch'], shape['cin']
+    H = W = (shape['size'] + p - 1) // p
+    K = cin * p * p
+    rows = B * H * W
+    # rows gather, linear, LayerNorm | LayerNorm, linear (dx for the feature gradient, dW), rows scatter
+    add('embed', 3, 3 + 2 + 1, 3 * (K * e + 3 * e), B * cin * shape['size'] ** 2 * 2 + rows * (6 * K + 11 * e))
+    for i, depth in enumerate(shape['depths']):
+        c, name = e * 2 ** i, 'stage{}'.format(i)
+        rows = B * H * W
+        table = (2 * WS - 1) ** 2 * HEADS[i]
+        nwin = ((H + WS - 1) // WS) * ((W + WS - 1) // WS)
+        scratch = 2 * 2 * B * nwin * HEADS[i] * ((2 * WS - 1) ** 2 + 2 * c // HEADS[i])
+        for _ in range(depth):
+            # forward as inference + the stored GELU pre-activation; backward: 2 LayerNorms (x and dy twice, dx), 4 linears
+            # (dy twice, x, dx, the pre-activation twice), the attention (qkv, dout, dqkv, the f64 partial rows twice)
+            add(name, 7, 2 * 3 + 4 * 2 + 2, 3 * (12 * c * c + 13 * c + table),
+                rows * (26 + 4) * c + rows * (10 + 8 + 7 + 4 + 18 + 10) * c + scratch, torch_ops=3)
+        if i < len(shape['depths']) - 1:
+            H2, W2 = (H + 1) // 2, (W + 1) // 2
+            r2 = B * H2 * W2
+            add(name, 3, 2 + 3 + 1, 3 * (8 * c + 8 * c * c), rows * c * 2 + r2 * (4 * c * 4 + 2 * c) + r2 * (4 * c * 8 + 2 * c * 2))
+            H, W = H2, W2
+    c = e * 2 ** (len(shape['depths']) - 1)
+    add('norm', 1, 3, 3 * 2 * c, 7 * B * H * W * c)
+    for s in range(shape['steps']):
+        co = c // 2
+        big = B * 4 * H * W * co
+        # pack 2, convolutions 2, statistics 3, apply 1 | BatchNorm 3, 1x1: weight gradient 2, pack 1, input gradient 1;
+        # transposed: bias gradient 2, weight gradient 2, pack 1, input gradient 1
+        add('decoder', 8, 13, 4 * (9 * c * co + co * co) + 12 * co, B * H * W * c * 4 + big * (2 + 2 + 3 + 2) + big * (5 + 4 + 3),
+            torch_ops=8)
+        c, H, W = co, 2 * H, 2 * W
+    jp = (shape['joints'] + 15) // 16 * 16
+    # pack, 1x1, layout, softmax | softmax, layout, pack, input gradient, weight gradient 2, bias gradient 2
+    add('decoder', 4, 8, 4 * (c * jp + jp), B * H * W * (3 * c + 6 * jp + 8 * shape['joints']), torch_ops=3)
+    total = {k: sum(s[k] for s in stages.values()) for k in ('forward_launches', 'backward_launches', 'torch_launches',
+                                                             'weight_bytes', 'activation_bytes')}
+    total['floor_us'] = 1e6 * (total['weight_bytes'] + total['activation_bytes']) / HBM_BYTES_PER_S
+    return {'blocks': sum(shape['depths']), 'stages': stages, 'total': total}
 
 
 # ---- the head from torch ops ------------------------------------------------------------------------------------------
@@ -250,17 +315,83 @@ def measure(B, repeats, warmup):
     return out
 
 
+def measure_train(B, repeats, warmup):
+    """forward + backward of the head in training mode: the HIP path under autograd and the torch composition under
+    autograd, on the same parameters and inputs, alternating; the gradient of a fixed random weighting of the heat maps"""
+    import torch
+    from config import get_cfg_defaults
+    from models import swin_transformer
+    cfg = get_cfg_defaults()
+    cfg.merge_from_file(YAML)
+    torch.manual_seed(0)
+    model = swin_transformer.get_pose_net(cfg, is_train=True, trainable=True, drop_path_rate=0.).cuda().train()
+    with torch.no_grad():
+        for k, v in model.named_parameters():
+            if k.endswith(('relative_position_bias_table', '.bias')):
+                v.normal_(0.0, 0.2)
+    g = torch.Generator(device='cuda').manual_seed(1)
+    x = torch.randn(B, SHAPE['cin'], SHAPE['size'], SHAPE['size'], device='cuda', generator=g).requires_grad_(True)
+    wgt = torch.randn(B, SHAPE['joints'], SHAPE['size'], SHAPE['size'], device='cuda', generator=g)
+    params = [v for k, v in model.named_parameters() if not k.startswith('backbone.') and v.requires_grad]
+    tp, n = TorchPath(model), model.swinTransformer.num_layers
+
+    def torch_head():
+        s = tp.embed(x)
+        for i in range(n):
+            s = tp.stage(i, *s)
+        return tp.decoder(*tp.norm(*s))
+
+    heads = {'hip': lambda: model.head_forward(x), 'torch': torch_head}
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times, grads = {}, {}
+
+    def step(name):
+        out = heads[name]()
+        grads[name] = torch.autograd.grad((out * wgt).sum(), [x] + params, allow_unused=True)[0]
+
+    for r in range(warmup + repeats):
+        for name in heads:
+            t = _time(lambda: step(name), start, stop)
+            if r >= warmup:
+                times.setdefault('train_' + name, []).append(t)
+            t = _time(lambda: heads[name](), start, stop)
+            if r >= warmup:
+                times.setdefault('forward_' + name, []).append(t)
+    out = {k: {'median_us': statistics.median(v), 'min_us': min(v), 'max_us': max(v)} for k, v in times.items()}
+    out['relative_difference_of_the_two_feature_gradients'] = float(
+        (grads['hip'] - grads['torch']).abs().max() / grads['torch'].abs().max())
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 32])
     ap.add_argument('--repeats', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--counts-only', action='store_true')
+    ap.add_argument('--train', action='store_true', help='time the training step of the head (forward + backward)')
     args = ap.parse_args(argv)
     if not args.counts_only:
         import torch
         if not torch.cuda.is_available():
             sys.exit('bench_swin: no HIP device: the timings need one (--counts-only prints the cost model)')
+    if args.train:
+        lines = []
+        for B in args.batches:
+            row = {'B': B, 'train_counts': train_counts(B)}
+            if not args.counts_only:
+                row['times'] = t = measure_train(B, args.repeats, args.warmup)
+                row['train_ratio_torch_over_hip'] = t['train_torch']['median_us'] / t['train_hip']['median_us']
+                lines.append('B {:3d}  '.format(B) + '  '.join('{} {:.0f} ({:.0f} .. {:.0f}) us'.format(
+                    k, v['median_us'], v['min_us'], v['max_us']) for k, v in sorted(t.items()) if isinstance(v, dict)))
+            print(json.dumps(row))
+        if lines:
+            path = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'profiles',
+                                'swin_train_times.txt')
+            with open(path, 'a') as f:
+                f.write('bench_swin.py --train: median (min .. max) of {} after {} warm-ups\n'.format(
+                    args.repeats, args.warmup) + '\n'.join(lines) + '\n')
+        return
     for B in args.batches:
         row = {'B': B, 'counts': counts(B)}
         if not args.counts_only:

@@ -1062,7 +1062,7 @@ int hrnet_tf_add_rows(const float* x, const float* pos, float* y, long long rows
 
 /*
  * Swin kernels of swin_transformer, the reference's SwinPose (csrc/swin.hip; reference lib/models/swin_transformer.py).
- * Forward only. Everything is f32, row-major, 64-bit element offsets, no float atomics: a call is bit-reproducible. Every
+ * Everything is f32, row-major, 64-bit element offsets, no float atomics: a call is bit-reproducible. Every
  * entry refuses what it has no kernel for (HR_E_BADARG) before it launches anything. The query takes (op, a, b):
  * HR_SWIN_ATTENTION (ws, hd): 1 <= ws * ws <= 64, 1 <= hd <= 128; HR_SWIN_MERGE (C, unused): 1 <= 4 C <= 65536;
  * HR_SWIN_EMBED (Cin, p): 1 <= Cin * p * p <= 65536.
@@ -1092,6 +1092,47 @@ int hrnet_swin_attention(const float* qkv, const float* qkv_bias, const float* b
 int hrnet_swin_merge_ln(const float* x, const float* gamma, const float* beta, float* y, int B, int H, int W, int C,
                         float eps, hr_stream_t stream);
 int hrnet_swin_patch_rows(const float* x, float* rows, int B, int Cin, int H, int W, int p, hr_stream_t stream);
+
+/*
+ * Backward of the Swin kernels (csrc/swin.hip), for training SwinPose. Same ranges and argument checks as the forward
+ * entries, each before the first launch.
+ *
+ * Window attention backward: from qkv, qkv_bias, bias_table (as the forward took them) and dout (B, H * W, heads * hd) it
+ * recomputes S = scale q k^T + table[rel] + mask and P = softmax(S) per (image, window, head) - nothing is saved by the
+ * forward - and gives dV = P^T dO, dP = dO v^T, dS = P (dP - rowsum(P dP)), dq = scale dS k, dk = scale dS^T q; the -100
+ * mask is a constant. dqkv (B, H * W, 3, heads, hd): a real token lies in one window, its row is written once. A token of
+ * the padded border has q = k = v = the qkv bias: as a key its dk and dv go to dqkv_bias (3 * heads * hd), the k and v
+ * thirds, head h's slice; as a query its output row was dropped, so its dO row, its dS row and its dq are exactly zero and
+ * the q third of dqkv_bias is written as zeros. dqkv_bias is the attention's own contribution only (all zeros when no token
+ * is padded); the qkv linear's bias gradient is separate. dtable ((2 ws - 1)^2, heads): dtable[rel(n, m), h] = the sum of
+ * dS[n, m] over n, m < ws * ws (padded keys included), windows and images. dqkv_bias and dtable may each be NULL; with
+ * either given, scratch (8-byte aligned) must hold hrnet_swin_attention_bwd_scratch(B, H, W, heads, hd, ws) floats =
+ * 2 * workgroups * ((2 ws - 1)^2 + 2 hd): each workgroup sums its dS into the bins (one thread per bin) and its padded
+ * keys' dk, dv in a fixed order into its own row, and a second launch adds the rows per head in workgroup order. Those
+ * sums are f64 throughout (a row holds f64 values, two floats each). The query is pure host code and returns 0 for a
+ * shape the entry refuses (among them one whose rows would take more than 2^31 - 1 floats). dqkv must not alias qkv or dout; scratch must alias nothing.
+ *
+ * Merge scatter, the inverse of hrnet_swin_merge_ln with gamma = NULL: dy (B * ceil(H / 2) * ceil(W / 2), 4 C) ->
+ * dx (B, H, W, C); every pixel lies in one row and block, gradients at the zero padding of an odd H or W are dropped.
+ *
+ * Patch rows backward, the inverse of hrnet_swin_patch_rows: drows (B * ceil(H / p) * ceil(W / p), Cin * p * p) ->
+ * dx (B, Cin, H, W) NCHW; gradients at the padding right of W and below H are dropped.
+ *
+ * Deconvolution input gradient, for the decoder's ConvTranspose2d(Cin, Cout, 3, 2, 1, 1): du (B, 2 H, 2 W, Cout_p) NHWC ->
+ * dx (B, H, W, Cin_p), dx[b, i, j, ci] = sum over taps and co of du[b, 2 i - 1 + kh, 2 j - 1 + kw, co] * w[ci, co, kh, kw],
+ * w_packed = hrnet_pack_weights(mode 0) of the weight read as OIHW (Cin, Cout, 3, 3): [Cin_p][9][Cout_p]. It is the
+ * stride-2 3x3 convolution that hrnet_conv2d also computes; this entry exists for its summation: the 9 * Cout_p terms
+ * (3456 at 384 channels) are added in f64 from 32-term f32 MFMA chunks, where the convolution entry's single f32 chain
+ * misses the training tests' error rule at 768 -> 384 channels. Cout_p, Cin_p multiples of 4.
+ */
+hr_value_t hrnet_swin_attention_bwd_scratch(int B, int H, int W, int heads, int hd, int ws);
+int hrnet_swin_attention_bwd(const float* qkv, const float* qkv_bias, const float* bias_table, const float* dout,
+                             float* dqkv, float* dqkv_bias, float* dtable, float* scratch, long long scratch_floats,
+                             int B, int H, int W, int heads, int hd, int ws, int shift, float scale, hr_stream_t stream);
+int hrnet_swin_merge_scatter(const float* dy, float* dx, int B, int H, int W, int C, hr_stream_t stream);
+int hrnet_swin_patch_rows_bwd(const float* drows, float* dx, int B, int Cin, int H, int W, int p, hr_stream_t stream);
+int hrnet_swin_deconv_dgrad(const float* du, const float* w_packed, float* dx, int B, int H, int W, int Cout_p, int Cin_p,
+                            hr_stream_t stream);
 
 /*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
