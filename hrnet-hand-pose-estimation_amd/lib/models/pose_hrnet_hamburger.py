@@ -1,0 +1,363 @@
+"""HamNet, MODEL.NAME `pose_hrnet_hamburger` (reference lib/models/pose_hrnet_hamburger.py:17-84 with
+lib/models/hamburger/burger.py:123-201 HamburgerV2Plus, ham.py:14-117, :227-269 NMF2D and bread.py:20-49): a Hamburger
+block - a non-negative matrix factorisation of the feature map between two 1x1 convolutions - on the 480-channel features
+of pose_hrnet_softmax, and a spatial softmax. Inference only.
+
+forward(x): x (B, 3, H, W)
+  1. backbone -> features (B, 480, h, w) (slot 1 of pose_hrnet_softmax's output)                         hamburger.py:69
+  2. squeeze: Conv2d 3x3 480 -> E (no bias), BatchNorm on running statistics, ReLU; E = MODEL.EMB_DIM            :56, :73
+  3. hamburger (V2+): lower_bread Conv2d 1x1 E -> C (bias) + ReLU, C = S E (2 S E with DUAL_HAM); the ham(s): with
+     DUAL_HAM the first C / 2 channels go through ham_1 (spatial), the last through ham_2 (not), else all C through ham
+     (MODEL.SPATIAL); cheese Conv2d 1x1 C -> C / f (no bias) + BatchNorm + ReLU, f = CHEESE_FACTOR (doubled when dual);
+     upper_bread Conv2d 1x1 C / f -> E (no bias); out = relu(coef_ham * x + coef_shortcut * shortcut)       burger.py:183-201
+  4. align: Conv2d 3x3 E -> 256 (no bias), BatchNorm, ReLU; fc: Dropout2d (identity here), Conv2d 1x1 256 -> J   :61-63
+  5. softmax(maps * trainable_temp) over the positions of each map                                               :79-82
+returns (heatmap_pred (B, J, h, w), trainable_temp).
+
+A ham (NMF2D in eval mode) reads its channels as G = B S matrices X (D, N) - spatial: D = channels / S, N = h w; not
+spatial: D = h w, N = channels / S - draws bases (G, D, R) with torch.rand on the HOST from the global CPU generator (ham_1
+before ham_2), normalises them along D, and runs
+    coef = softmax_R(X^T bases); EVAL_STEPS times {coef *= X^T bases / (coef bases^T bases + 1e-6);
+    bases *= X coef / (bases coef^T coef + 1e-6)}; one more coef update; out = bases coef^T.
+MODEL.INV_T has no effect (NMF2D sets its inv_t to 1, ham.py:231).
+
+Every product is a launch through the C ABI. The head runs NHWC: the features are turned once (hrnet_nchw_to_nhwc), and
+the hams are hipnet.nmf on views of lower_bread's output - the spatial ham reads its channel half as X^T, the other as X,
+nothing is copied - and write their reconstructions straight into their channels of the cheese input (no cat). The
+convolutions, all f32 on existing entries:
+  squeeze, align   the 3x3 as nine 1x1 launches over displaced windows that accumulate (hrnet_conv2d_dilated3x3, dilation
+                   1): nine sums of 480 / 512 terms in place of hrnet_conv2d's single chain of 4320 / 4608, whose error
+                   alone was 2.5e-6 / 2.0e-6 of max|.| at full size against 6.6e-7 / 5.4e-7 this way
+  lower_bread, upper_bread, fc   hrnet_conv2d 1x1 on packed weights, bias in the launch
+  cheese           a plain product of the NMF engine, pixels x (C, C / f), the ham outputs read in place (a 1024-term sum
+                   in chunks of 256; hrnet_conv2d's chain gave 1.7e-6)
+An eval-mode BatchNorm is a folded (scale, shift) that the CONSUMER applies with the ReLU when it loads its input
+(hrnet_conv2d's in_scale / in_shift / in_relu). What stays in torch, small element-wise launches: the ReLU of lower_bread's
+output (the hams read it thirteen times, the convolution entry has no output activation); coef_shortcut *
+relu(bn(squeeze)) (addcmul, relu_, mul_; upper_bread, its weight scaled by coef_ham when it is packed, then ACCUMULATES
+into that buffer) and the block's closing relu_ (the tap-wise align has no prologue); and the L2-normalisation of the fresh
+bases. The packed weights are built once and rebuilt when a head parameter or buffer changes (load_state_dict, .cuda()).
+
+The holder modules are ordinary nn.Conv2d / nn.BatchNorm2d under the reference's attribute names, so state_dict() has
+the reference's keys in the reference's order and a reference checkpoint loads with strict=True; their own forward is never
+used.
+
+Refused when the model is built, each naming its key: MODEL.HAM_TYPE other than 'NMF' (VQ and CD are not built),
+MODEL.VERSION other than 'V2+', MODEL.RAND_INIT false (the persistent bases buffer and its online update), a
+MODEL.BACKBONE_NAME without 'hrnet' (the ResNet backbone), MODEL.COMPUTE_DTYPE other than fp32, an S, R, EMB_DIM,
+CHEESE_FACTOR or EVAL_STEPS that does not fit. Refused in forward: CPU tensors (ValueError); training mode, and eval mode
+with a gradient required (NotImplementedError: SyncBN batch statistics, the backward through the last coefficient update
+and Dropout2d are not built - run model.eval() under torch.no_grad()).
+"""
+import logging
+
+import torch
+import torch.nn as nn
+
+from hipnet import _capi as C
+from hipnet import nmf as N
+from hipnet import swin as S
+
+logger = logging.getLogger(__name__)
+
+NOT_BUILT = 'training of pose_hrnet_hamburger is not built'
+ALIGN_CHANNELS = 256
+BN_MOMENTUM = 3e-4            # bread.py:17
+
+
+def _unused(name):
+    def forward(self, *a, **k):
+        raise NotImplementedError('{} holds parameters of HamNet; HamNet.head_forward runs it through hipnet.nmf and the '
+                                  'convolution entry'.format(name))
+    return forward
+
+
+class ConvBNReLU(nn.Module):
+    def __init__(self, in_c, out_c, kernel_size=1):
+        super(ConvBNReLU, self).__init__()
+        self.conv = nn.Conv2d(in_c, out_c, kernel_size=kernel_size, stride=1, padding=kernel_size // 2, bias=False)
+        self.bn = nn.BatchNorm2d(out_c, momentum=BN_MOMENTUM)
+        self.act = nn.ReLU(inplace=True)
+
+    forward = _unused('ConvBNReLU')
+
+
+class NMF2D(nn.Module):
+    """holds the sizes of one ham; no parameters, and with RAND_INIT no buffers"""
+
+    def __init__(self, spatial, S_, R, steps):
+        super(NMF2D, self).__init__()
+        self.spatial, self.S, self.R, self.eval_steps = bool(spatial), int(S_), int(R), int(steps)
+
+    forward = _unused('NMF2D')
+
+    def sizes(self, B, channels, hw):
+        """(G, D, N) of this ham on `channels` channels of an hw-pixel map"""
+        per = channels // self.S
+        return (B * self.S, per, hw) if self.spatial else (B * self.S, hw, per)
+
+
+class HamburgerV2Plus(nn.Module):
+    def __init__(self, config, in_c):
+        super(HamburgerV2Plus, self).__init__()
+        M = config.MODEL
+        S_, D, R, steps = int(M.S), emb_dim(config), int(M.R), int(M.EVAL_STEPS)
+        self.dual = bool(M.DUAL_HAM)
+        C_ = S_ * D * (2 if self.dual else 1)
+        # own parameters precede the sub-modules in a state dict, as the reference's lists them
+        self.coef_shortcut = nn.Parameter(torch.tensor([1.]))
+        self.coef_ham = nn.Parameter(torch.tensor([0. if M.ZERO_HAM else 1.]))
+        self.lower_bread = nn.Sequential(nn.Conv2d(in_c, C_, 1), nn.ReLU(inplace=True))
+        if self.dual:
+            self.ham_1 = NMF2D(True, S_, R, steps)
+            self.ham_2 = NMF2D(False, S_, R, steps)
+        else:
+            self.ham = NMF2D(M.SPATIAL, S_, R, steps)
+        factor = int(M.CHEESE_FACTOR) * (2 if self.dual else 1)
+        self.channels, self.mid = C_, C_ // factor
+        self.cheese = ConvBNReLU(C_, C_ // factor)
+        self.upper_bread = nn.Conv2d(C_ // factor, in_c, 1, bias=False)
+        self.shortcut = nn.Sequential()
+        for m in self.modules():                       # burger.py:173-181
+            if isinstance(m, nn.Conv2d):
+                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+                m.weight.data.normal_(0, (2. / n) ** 0.5)
+
+    forward = _unused('HamburgerV2Plus')
+
+    def hams(self):
+        """[(ham, first channel, channels)] in the reference's drawing order"""
+        if self.dual:
+            return [(self.ham_1, 0, self.channels // 2), (self.ham_2, self.channels // 2, self.channels // 2)]
+        return [(self.ham, 0, self.channels)]
+
+
+def emb_dim(config):
+    e = config.MODEL.EMB_DIM
+    if isinstance(e, (list, tuple)):
+        if len(e) != 1:
+            raise ValueError('MODEL.EMB_DIM {}: pose_hrnet_hamburger takes one width (an int or a one-element '
+                             'list)'.format(e))
+        e = e[0]
+    return int(e)
+
+
+def check_config(config):
+    """what the model refuses of a config, before anything is built"""
+    M = config.MODEL
+    if M.HAM_TYPE != 'NMF':
+        raise ValueError('MODEL.HAM_TYPE {!r}: only \'NMF\' is built (the VQ and CD hams are not)'.format(M.HAM_TYPE))
+    if M.VERSION != 'V2+':
+        raise ValueError('MODEL.VERSION {!r}: only the \'V2+\' burger is built (V1 and V2 are not)'.format(M.VERSION))
+    if not M.RAND_INIT:
+        raise ValueError('MODEL.RAND_INIT false: the persistent bases buffer and its online update are not built')
+    if 'hrnet' not in M.BACKBONE_NAME:
+        raise ValueError('MODEL.BACKBONE_NAME {!r}: pose_hrnet_hamburger is built on \'pose_hrnet_softmax\' (the ResNet '
+                         'backbone is not built)'.format(M.BACKBONE_NAME))
+    if M.BACKBONE_NAME != 'pose_hrnet_softmax':
+        raise ValueError('MODEL.BACKBONE_NAME {!r}: the HRNet backbone that hands out its features is '
+                         '\'pose_hrnet_softmax\''.format(M.BACKBONE_NAME))
+    if str(M.COMPUTE_DTYPE).lower() not in ('fp32', 'float32'):
+        raise ValueError('MODEL.COMPUTE_DTYPE {!r}: pose_hrnet_hamburger runs in fp32 only (bf16 is not built)'.format(
+            M.COMPUTE_DTYPE))
+    e, s, r, f = emb_dim(config), int(M.S), int(M.R), int(M.CHEESE_FACTOR)
+    if e < 1 or s < 1 or r < 1:
+        raise ValueError('MODEL.EMB_DIM {}, MODEL.S {}, MODEL.R {}: each must be at least 1'.format(e, s, r))
+    if f < 1 or (s * e) % f:
+        raise ValueError('MODEL.CHEESE_FACTOR {}: must divide the S * EMB_DIM = {} channels of a ham'.format(f, s * e))
+    if int(M.EVAL_STEPS) < 0:
+        raise ValueError('MODEL.EVAL_STEPS {}: must be at least 0'.format(M.EVAL_STEPS))
+    if not N.supported(N.OP_UPDATE, s * e, r):
+        raise ValueError('MODEL.EMB_DIM {} with MODEL.R {}: beyond the NMF kernels'.format(e, r))
+    if int(M.NUM_JOINTS) != int(config.DATASET.NUM_JOINTS):
+        raise ValueError('MODEL.NUM_JOINTS {} differs from DATASET.NUM_JOINTS {}'.format(M.NUM_JOINTS,
+                                                                                         config.DATASET.NUM_JOINTS))
+
+
+def conv_nhwc(x, packed, cout, ks, bias=None, in_affine=None, in_relu=False, into=None):
+    """f32 NHWC stride-1 convolution on hrnet_conv2d: x (B, H, W, Cin), packed [cout][ks * ks][Cin]; in_affine: the
+    producer's folded BatchNorm (scale, shift), applied with in_relu when x is loaded; `into`: accumulate into this
+    (B, H, W, cout) tensor instead of writing a new one"""
+    B, H, W, cin = x.shape
+    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device) if into is None else into
+    scale, shift = (None, None) if in_affine is None else in_affine
+    with torch.cuda.device(x.device):
+        C.call('hrnet_conv2d', C.HR_F32, x.data_ptr(), packed.data_ptr(), C.ptr(scale), C.ptr(shift), C.ptr(bias),
+               y.data_ptr(), None, B, H, W, cin, H, W, cout, ks, 1, 0, 1 if in_relu else 0, 0 if into is None else 1,
+               C.stream_ptr())
+    return y
+
+
+def conv3x3_taps(x, taps, cout):
+    """the same 3x3 convolution as nine 1x1 launches over displaced windows that accumulate into y
+    (hrnet_conv2d_dilated3x3 with dilation 1): nine sums of Cin terms in place of one of 9 Cin. x (B, H, W, Cin) as it is (no
+    prologue), taps [9][cout][Cin] of _pack_taps; no bias"""
+    B, H, W, cin = x.shape
+    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        C.call('hrnet_conv2d_dilated3x3', C.HR_F32, x.data_ptr(), taps.data_ptr(), 4 * cout * cin, y.data_ptr(), B, H, W, cin,
+               cout, 1, C.stream_ptr())
+    return y
+
+
+def _pack_taps(weight, cin_pad, cout_pad):
+    """OIHW 3x3 weight -> nine packed 1x1 matrices [9][cout_pad][cin_pad], tap t = 3 r + s"""
+    return torch.cat([_pack(weight[:, :, t // 3:t // 3 + 1, t % 3:t % 3 + 1], cin_pad, cout_pad) for t in range(9)])
+
+
+def _pack(weight, cin_pad, cout_pad, scale=None):
+    """OIHW weight, optionally scaled per output channel, -> [cout_pad][ks * ks][cin_pad] on the device"""
+    w = weight.detach().float()
+    if scale is not None:
+        w = (w.double() * scale.double().reshape(-1, 1, 1, 1)).float()
+    w = w.contiguous()
+    co, ci, ks, _ = w.shape
+    out = torch.empty(cout_pad * ks * ks * cin_pad, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        C.call('hrnet_pack_weights', C.HR_F32, w.data_ptr(), out.data_ptr(), co, ci, ks, cout_pad, cin_pad, 0, C.stream_ptr())
+    return out
+
+
+def _padded(v, n):
+    out = torch.zeros(n, dtype=torch.float32, device=v.device)
+    out[:v.numel()] = v.detach().float().reshape(-1)
+    return out
+
+
+def _fold(bn):
+    """eval-mode BatchNorm as (scale, shift), float64"""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return scale, bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+
+
+class HamNet(nn.Module):
+    def __init__(self, config, is_train=False):
+        super(HamNet, self).__init__()
+        check_config(config)
+        M = config.MODEL
+        # own parameters precede the sub-modules in a state dict, as the reference's lists them
+        self.trainable_temp = nn.Parameter(torch.tensor(1.0), requires_grad=bool(M.TRAINABLE_SOFTMAX))
+        from models import pose_hrnet_softmax
+        self.in_channel = sum(M.EXTRA.STAGE4.NUM_CHANNELS)
+        self.backbone = pose_hrnet_softmax.get_pose_net(config, is_train=True)
+        path = M.BACKBONE_MODEL_PATH
+        if path and is_train:                                   # the reference loads it when training only (:29)
+            checkpoint = torch.load(path, map_location='cpu')
+            state = checkpoint['state_dict'] if 'state_dict' in checkpoint else checkpoint
+            logger.info("=> Loading pretrained {} backbone from '{}'".format(M.BACKBONE_NAME, path))
+            self.backbone.load_state_dict({k.replace('module.', ''): v for k, v in state.items()}, strict=False)
+        for p in self.backbone.parameters():
+            p.requires_grad = False
+        e = emb_dim(config)
+        self.embed_dim, self.num_joints = e, int(config.DATASET.NUM_JOINTS)
+        self.squeeze = ConvBNReLU(self.in_channel, e, 3)
+        self.hamburger = HamburgerV2Plus(config, in_c=e)
+        self.align = ConvBNReLU(e, ALIGN_CHANNELS, 3)
+        self.fc = nn.Sequential(nn.Dropout2d(p=0.1), nn.Conv2d(ALIGN_CHANNELS, self.num_joints, 1))
+        self._plan, self._plan_key = None, None
+
+    # ---- the packed weights ----------------------------------------------------------------------------------------
+    def _head_tensors(self):
+        return [t for m in (self.squeeze, self.hamburger, self.align, self.fc) for t in
+                list(m.parameters()) + list(m.buffers())]
+
+    def _head_plan(self):
+        """packed weights of the convolutions and the folded BatchNorms (scale, shift) their consumers apply; built once,
+        rebuilt when a head parameter or buffer was written or moved"""
+        key = tuple((t.data_ptr(), t._version) for t in self._head_tensors())
+        if self._plan is not None and key == self._plan_key:
+            return self._plan
+        h = self.hamburger
+        cin, e = S.pad16(self.in_channel), S.pad16(self.embed_dim)
+        cp, mp, ap, jp = S.pad16(h.channels), S.pad16(h.mid), S.pad16(ALIGN_CHANNELS), S.pad16(self.num_joints)
+        affine = lambda bn, n: tuple(_padded(v, n) for v in _fold(bn))
+        # the cheese as the (C, mid) matrix of a plain NMF-engine product, zero columns up to the padded width
+        w_cheese = torch.zeros((h.channels, mp), dtype=torch.float32, device=h.cheese.conv.weight.device)
+        w_cheese[:, :h.mid] = h.cheese.conv.weight.detach().float().reshape(h.mid, h.channels).t()
+        self._plan = dict(
+            cin=cin, e=e, cp=cp, mp=mp, ap=ap, jp=jp,
+            w_squeeze=_pack_taps(self.squeeze.conv.weight, cin, e), bn_squeeze=affine(self.squeeze.bn, e),
+            w_lower=_pack(h.lower_bread[0].weight, e, cp), b_lower=_padded(h.lower_bread[0].bias, cp),
+            w_cheese=w_cheese, bn_cheese=affine(h.cheese.bn, mp),
+            w_upper=_pack(h.upper_bread.weight, mp, e, h.coef_ham.detach().double().expand(self.embed_dim)),
+            w_align=_pack_taps(self.align.conv.weight, e, ap), bn_align=affine(self.align.bn, ap),
+            w_fc=_pack(self.fc[1].weight, ap, jp), b_fc=_padded(self.fc[1].bias, jp))
+        self._plan_key = key
+        return self._plan
+
+    # ---- the bases -------------------------------------------------------------------------------------------------
+    def bases_shapes(self, B, h, w):
+        """the (G, D, R) of every ham's bases for B images of h x w features, in drawing order"""
+        return [(g, d, ham.R) for ham, _, ch in self.hamburger.hams() for g, d, _ in [ham.sizes(B, ch, h * w)]]
+
+    def draw_bases(self, B, h, w):
+        """the reference's draw, on the host: torch.rand((B * S, D, R)) from the global CPU generator, ham_1 before ham_2;
+        float32 CPU tensors, not yet normalised"""
+        return [N.draw_bases(*shape) for shape in self.bases_shapes(B, h, w)]
+
+    # ---- the model -------------------------------------------------------------------------------------------------
+    def _refuse(self, x):
+        if self.training:
+            raise NotImplementedError('HamNet: {} (SyncBN batch statistics, the backward through the last coefficient '
+                                      'update and Dropout2d are a later step): call .eval() and run under '
+                                      'torch.no_grad()'.format(NOT_BUILT))
+        if torch.is_grad_enabled() and (getattr(x, 'requires_grad', False) or
+                                        any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('HamNet: eval mode with a gradient required is refused - {}: run under '
+                                      'torch.no_grad()'.format(NOT_BUILT))
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError('HamNet: expected HIP-device tensors (there is no CPU path in this build)')
+        if self.trainable_temp.device != x.device:
+            raise ValueError('HamNet: the model is on {} and the input on {}: move the model with .cuda()'.format(
+                self.trainable_temp.device, x.device))
+
+    def head_forward(self, features, bases=None):
+        """features (B, 480, h, w) NCHW on the device -> heat maps: everything after the backbone. bases: None (drawn here
+        as the reference draws them), or a list of one tensor per ham, (B * S, D, R), NOT yet normalised (CPU or device)"""
+        self._refuse(features)
+        if features.ndim != 4 or features.shape[1] != self.in_channel or features.numel() == 0:
+            raise ValueError('features {}: expected (B, {}, h, w)'.format(tuple(features.shape), self.in_channel))
+        B, _, hh, ww = features.shape
+        shapes = self.bases_shapes(B, hh, ww)
+        if bases is None:
+            bases = self.draw_bases(B, hh, ww)
+        bases = list(bases) if isinstance(bases, (list, tuple)) else [bases]
+        if len(bases) != len(shapes) or any(tuple(b.shape) != s for b, s in zip(bases, shapes)):
+            raise ValueError('bases {}: expected {}'.format([tuple(b.shape) for b in bases], shapes))
+        with torch.no_grad():
+            p = self._head_plan()
+            dev = features.device
+            x = torch.empty((B, hh, ww, p['cin']), dtype=torch.float32, device=dev)
+            f = features.detach().float().contiguous()
+            with torch.cuda.device(dev):
+                C.call('hrnet_nchw_to_nhwc', C.HR_F32, f.data_ptr(), x.data_ptr(), B, hh, ww, p['cin'], self.in_channel,
+                       C.stream_ptr())
+            z = conv3x3_taps(x, p['w_squeeze'], p['e'])                               # squeeze before its BatchNorm
+            low = conv_nhwc(z, p['w_lower'], p['cp'], 1, bias=p['b_lower'], in_affine=p['bn_squeeze'], in_relu=True).relu_()
+            h = self.hamburger
+            cheese_in = torch.empty_like(low)             # the hams write every real channel; no other is read
+            for (ham, c0, ch), b in zip(h.hams(), bases):
+                b = N.normalise_bases(b.to(device=dev, dtype=torch.float32))
+                xin = low.permute(0, 3, 1, 2)[:, c0:c0 + ch]                          # (B, ch, h, w) view of the NHWC map
+                N.nmf2d(xin, b, ham.eval_steps, ham.spatial, ham.S, out=cheese_in.permute(0, 3, 1, 2)[:, c0:c0 + ch])
+            # cheese before its BatchNorm: rows of pixels times the (C, mid) matrix, the channels read as X^T in place
+            # (one matrix over the pixels of all images)
+            mid = N.product(cheese_in.reshape(1, B * hh * ww, p['cp']).transpose(1, 2)[:, :h.channels],
+                            p['w_cheese'].unsqueeze(0)).reshape(B, hh, ww, p['mp'])
+            scale, shift = p['bn_squeeze']
+            block = torch.addcmul(shift, z, scale).relu_().mul_(h.coef_shortcut.detach())
+            # + coef_ham * upper_bread(relu(bn(mid))); the block's own ReLU, then align before its BatchNorm
+            conv_nhwc(mid, p['w_upper'], p['e'], 1, in_affine=p['bn_cheese'], in_relu=True, into=block)
+            y = conv3x3_taps(block.relu_(), p['w_align'], p['ap'])
+            y = conv_nhwc(y, p['w_fc'], p['jp'], 1, bias=p['b_fc'], in_affine=p['bn_align'], in_relu=True)
+            return S.heatmap_softmax(y, self.num_joints, self.trainable_temp)
+
+    def forward(self, x, bases=None):
+        self._refuse(x)
+        with torch.no_grad():
+            features = self.backbone(x)[1]
+        return self.head_forward(features, bases), self.trainable_temp
+
+
+def get_pose_net(cfg, is_train, **kwargs):
+    return HamNet(cfg, is_train, **kwargs)

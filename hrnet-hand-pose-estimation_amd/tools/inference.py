@@ -28,7 +28,7 @@ from config import cfg, update_config
 from core.evaluate2d import load_checkpoint_state
 from dataset.preprocess import (IMAGE_EXTENSIONS, VIDEO_EXTENSIONS, list_images, pack_images, read_image_rgb,
                                 resize_normalize, sequence_windows)
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_softmax, swin_transformer  # noqa: F401
+from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, swin_transformer  # noqa: F401
 from utils.heatmap_decoding import get_final_preds
 
 # the reference's per-finger colours (tools/inference.py:170-185): wrist -> palm -> ... -> tip

@@ -1135,6 +1135,47 @@ int hrnet_swin_deconv_dgrad(const float* du, const float* w_packed, float* dx, i
                             hr_stream_t stream);
 
 /*
+ * NMF kernels of pose_hrnet_hamburger, the reference's HamNet (csrc/nmf.hip; reference lib/models/hamburger/ham.py, NMF2D
+ * :227-269 on _MatrixDecomposition2DBase :14-117). Everything is f32, 64-bit element offsets, no float atomics: every sum
+ * has one fixed order, so a call is bit-reproducible. Products run on mfma_f32_16x16x4f32; any size >= 1, edge tiles are
+ * bounds-checked in the kernel; an operand is read with 16-byte accesses when its pointer is 16-byte aligned and its
+ * leading dimension and batch stride are multiples of 4, with element-wise loads in the same kernel otherwise. Every entry
+ * refuses what it has no kernel for (HR_E_BADARG) before it launches anything. The query takes (op, a, b): HR_NMF_UPDATE
+ * (K, R), HR_NMF_GRAM (K, R), HR_NMF_PRODUCT (K, R): each 1 .. 2^24; batches G: 1 .. 65535.
+ *
+ * The feature matrix is never copied or transposed: an entry that reads it takes (x, ldx, bsx, xt) and reads
+ * op(X)_g[i, k] = x[g * bsx + i * ldx + k] (xt = 0) or x[g * bsx + k * ldx + i] (xt = 1), so a channel half of a wider
+ * NCHW or NHWC tensor and both orientations of a ham go through the same code. T, F, Gm and the results are dense
+ * row-major, batch after batch.
+ *
+ * Update, the multiplicative step (:246-257): Tout = T * (op(X) F) / (T Gm + eps) for T, Tout (G, M, R), F (G, K, R),
+ * op(X) (G, M, K), Gm (G, R, R). Both products of an output tile are accumulated in registers and the ratio is taken
+ * there: neither reaches memory. Out of place (a tile's T Gm reads whole rows of T). Coefficients: (T, F, op(X)) =
+ * (coef, bases, X^T) with Gm = bases^T bases; bases: (bases, coef, X) with Gm = coef^T coef.
+ *
+ * Gram: Gm (G, R, R) = A^T A for A (G, K, R). A long K is split over workgroups; the parts go through `scratch`, at least
+ * hrnet_nmf_gram_scratch(G, K, R) floats (0 when nothing is split: scratch may then be NULL), and are added in split
+ * order by a second launch. The query is pure host code and returns 0 for a shape the entry refuses (among them one whose
+ * parts would take more than 2^31 - 1 floats).
+ *
+ * Product: out (G, M, R) = op(X) F, the logits of the initial softmax (:51; the row softmax itself is
+ * hrnet_spatial_softmax_fwd on G * M rows of R). Reconstruct (:93): out_g[d, n] = sum_r Bs[d, r] Cf[n, r] for Bs (G, D, R),
+ * Cf (G, N, R), stored at out[g * bso + d * ldo + n] (ot = 0) or out[g * bso + n * ldo + d] (ot = 1): a ham's result goes
+ * straight into its channels of the next layer's input.
+ */
+enum { HR_NMF_UPDATE = 0, HR_NMF_GRAM = 1, HR_NMF_PRODUCT = 2 };
+hr_value_t hrnet_nmf_supported(int op, int a, int b);
+int hrnet_nmf_update(const float* T, const float* F, const float* x, long long ldx, long long bsx, int xt, const float* Gm,
+                     float* Tout, int G, int M, int K, int R, float eps, hr_stream_t stream);
+hr_value_t hrnet_nmf_gram_scratch(int G, int K, int R);
+int hrnet_nmf_gram(const float* A, float* Gm, float* scratch, long long scratch_floats, int G, int K, int R,
+                   hr_stream_t stream);
+int hrnet_nmf_product(const float* x, long long ldx, long long bsx, int xt, const float* F, float* out, int G, int M, int K,
+                      int R, hr_stream_t stream);
+int hrnet_nmf_reconstruct(const float* Bs, const float* Cf, float* out, long long ldo, long long bso, int ot, int G, int D,
+                          int N, int R, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
