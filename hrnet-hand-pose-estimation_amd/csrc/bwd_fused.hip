@@ -198,45 +198,11 @@ __global__ __launch_bounds__(NW * 64) void bwd_fused_kernel(BwdArgs a) {
 #endif
   FSTAMP();
 
-  // ---- weights of this input-channel block: resident for the whole walk ----
-  {
-    const int v = tid % VPG;
-#pragma unroll
-    for (int k = 0; k < XW; ++k) {
-      const int idx = tid + k * NT;
-      if (idx < WVECS) {
-        const int rt = idx / VPG;
-        const int tp = rt % 9, q = rt / 9;          // LDS row q holds the channel the MFMA row order needs
-        const int ci = c0 + ((q & 15) >> 2) * 8 + (q >> 4) * 4 + (q & 3);
-        const int co = v * VEC;
-        V16 w = v16_zero();
-        if (ci < a.Cin && co < a.Cout) w = *(const V16*)(a.wT + ((size_t)(ci * 9 + tp) * a.Cout + co) * ES);
-        *(V16*)(wl + ((tp * NKK + (v >> 2)) * CB + q) * 64 + (((v & 3) ^ lds_swz<64>(q)) << 4)) = w;
-      }
-    }
-  }
-
-  FSTAMP();
-  // coefficient tables (read back per tile: a dependent global load inside the staging pass costs its full latency)
+  // Everything up to the first store_tile depends on kernel arguments only, so all of it is requested before anything
+  // is waited for (one memory round trip instead of four in a row): the first tile's loads, then the weights, then the
+  // rows and per-channel values of the coefficient build; the address arithmetic of the matrix phases sits between the
+  // requests and the first wait.
   const bool from_rows = a.ref.rows != nullptr;
-  if (from_rows) {
-    static_assert(NT * 2 * 8 <= GBYTES, "row-sum scratch fits the g image");
-    hr_bnbwd_coef_from_rows<NT, COP>(a.ref, a.Cout, (double*)gl, ctab, blockIdx.x == 0);
-  }
-  for (int i = tid; i < 3 * COP + 2 * CB; i += NT) {
-    float v = 0.f;
-    if (i < 3 * COP) {
-      if (from_rows) continue;
-      const int w = i / COP, c = i % COP;
-      if (a.coef && c < a.Cout) v = a.coef[w * a.Cout + c];
-    } else {
-      const int j = i - 3 * COP, w = j / CB, c = c0 + j % CB;
-      v = w == 0 ? 1.f : 0.f;
-      if (a.in_scale && c < a.Cin) v = w == 0 ? a.in_scale[c] : a.in_shift[c];
-    }
-    ctab[i] = v;
-  }
-  __syncthreads();   // the first staging pass reads the tables
   const int vg = tid % VPG, va = tid % VPA;
   const int cg = vg * VEC, ca = c0 + va * VEC;
   const bool cg_ok = cg < a.Cout, ca_ok = ca < a.Cin;
@@ -420,6 +386,48 @@ __global__ __launch_bounds__(NW * 64) void bwd_fused_kernel(BwdArgs a) {
     }
   };
 
+  // ---- requests: first tile, weights of this input-channel block, coefficient inputs ----
+  int t = split;
+  if (t < a.total_tiles) load_tile(t);
+  // weights (resident for the whole walk), by direct global->LDS loads: no registers, no LDS store pass. A wave
+  // instruction fills 64 consecutive 16-byte slots of the image, so a lane takes the SOURCE address of the vector that
+  // belongs in its slot: slot L = ((tap * NKK + k-chunk) * CB + row q) * 4 + chunk position, the vector at that position
+  // is v = k-chunk * 4 + (position ^ lds_swz<64>(q)) of channel ci(q). A vector of the channel padding gets an offset
+  // beyond the descriptor: zeros land in LDS. (Waited for with everything else, in front of the first barrier.)
+  {
+    static_assert(WVECS == 9 * NKK * CB * 4 && WVECS % 64 == 0, "the weight image is whole wave instructions");
+    typedef __attribute__((address_space(3))) void* lds_ptr_t;
+    const auto rdw = __builtin_amdgcn_make_buffer_rsrc((void*)a.wT, 0, a.Cin * 9 * a.Cout * ES, 0x00020000);
+#pragma unroll
+    for (int k = 0; k < XW; ++k) {
+      const int L0 = __builtin_amdgcn_readfirstlane(wave) * 64 + k * NT, L = L0 + lane;
+      const int q = (L >> 2) % CB, r = L / (4 * CB);          // LDS row q holds the channel the MFMA row order needs
+      const int kk = r % NKK, tp = r / NKK;
+      const int ci = c0 + ((q & 15) >> 2) * 8 + (q >> 4) * 4 + (q & 3);
+      const int co = (kk * 4 + ((L & 3) ^ lds_swz<64>(q))) * VEC;
+      const bool ok = ci < a.Cin && co < a.Cout;
+      if (L0 < WVECS)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rdw, (lds_ptr_t)(wl + L0 * 16), 16,
+                                                 ok ? (unsigned)(((ci * 9 + tp) * a.Cout + co) * ES) : OOB, 0, 0, 0);
+    }
+  }
+  // coefficient tables (read back per tile: a dependent global load inside the staging pass costs its full latency)
+  static_assert(3 * COP + 2 * CB <= NT, "one table entry per thread");
+  HrBnBwdIssued bst;
+  if (from_rows) hr_bnbwd_rows_issue<NT, COP>(a.ref, a.Cout, blockIdx.x == 0, bst);
+  float tabv = 0.f;
+  bool tab_own = false;     // this thread writes ctab[tid]
+  if (tid < 3 * COP) {
+    const int w = tid / COP, c = tid % COP;
+    tab_own = !from_rows;
+    if (!from_rows && a.coef && c < a.Cout) tabv = a.coef[w * a.Cout + c];
+  } else if (tid < 3 * COP + 2 * CB) {
+    const int j = tid - 3 * COP, w = j / CB, c = c0 + j % CB;
+    tab_own = true;
+    tabv = w == 0 ? 1.f : 0.f;
+    if (a.in_scale && c < a.Cin) tabv = w == 0 ? a.in_scale[c] : a.in_shift[c];
+  }
+
   // ---- per-lane operand offsets ----
   // input gradient D[ci 32][pixel 256]: a wave owns 32 pixels (2 fragments) x all 32 channels (2 fragments);
   // a lane ends up with 8 contiguous channels of one pixel per pixel fragment
@@ -498,8 +506,17 @@ __global__ __launch_bounds__(NW * 64) void bwd_fused_kernel(BwdArgs a) {
   constexpr int MF = ES == 2 ? 1 : 4;          // mma16<T>: one 16x16x32 bf16 MFMA or four 16x16x4 f32 ones
   constexpr int RDF = ES == 2 ? 2 : 4;         // trl<T>: two ds_read_b64_tr_b16 or four ds_read_b32
 
-  int t = split;
-  if (t < a.total_tiles) load_tile(t);
+  // ---- the one wait: this wave's weight vectors have landed in LDS (the barrier below hands them to the other waves;
+  // vector-memory loads return in order, so the first tile is in its registers as well), then the coefficient tables ----
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  FSTAMP();
+  if (tab_own) ctab[tid] = tabv;
+  if (from_rows) {
+    static_assert(NT * 2 * 8 <= GBYTES, "row-sum scratch fits the g image");
+    hr_bnbwd_coef_finish<NT, COP>(a.ref, a.Cout, bst, (double*)gl, ctab, blockIdx.x == 0);   // (ends with a barrier)
+  } else {
+    __syncthreads();   // the first staging pass reads the tables
+  }
   if HR_ABLATE(a, 8) { okg = oka = 0; }
   FSTAMP();
   for (; t < a.total_tiles; t += a.nsplit) {

@@ -21,6 +21,10 @@
 
 #include "common.h"
 
+#ifndef HR_PW_PREFETCH
+#define HR_PW_PREFETCH 1     // 1: the next tile's dz / y / x are requested into registers right after the staging barrier of the current one; 0: at the top of the next tile (measurement builds)
+#endif
+
 namespace {
 
 struct PwArgs {
@@ -72,6 +76,15 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
   constexpr bool ROWS = CI <= 64;                               // statistics in registers: 2 x CI/4 per lane
   constexpr bool ROWS2 = !ROWS;                                 // 256 channels: through the LDS tile, per staging thread
   constexpr bool AFF = CI <= 64;                                // input affine (a 256-channel input is a stored activation)
+  // HOIST: the first tile is requested in the prologue, together with the weights and the coefficient inputs, and
+  // every later one inside the tile before it (PREFETCH: right after its staging barrier, so that it is in flight under
+  // the matrix phases). Only the 64 -> 64 layer takes it. Measured alone at 64 x 64 x 64 pixels, parent / hoist without
+  // prefetch / hoist with prefetch: 47.0 / 39.4 / 38.2 us there, but 140.8 / 156.4 / 146.0 us with 256 input channels
+  // (one wave per SIMD, 248 + 148 registers), and with 256 output channels the tile is 72 registers of a kernel that
+  // stands at 256 with two workgroups per CU - held across the prologue or the matrix phases they spill (92 - 176
+  // bytes of scratch per lane). Those two keep their loads at the top of the tile.
+  constexpr bool HOIST = CO <= 64 && CI <= 64;
+  constexpr bool PREFETCH = HR_PW_PREFETCH != 0 && HOIST;
   static_assert(TP * VPG % NT == 0 && TP * VPA % NT == 0 && FCO % COSPLIT == 0 && FCI % CISPLIT == 0, "geometry");
   static_assert(GBYTES + ABYTES + WBYTES <= 80 * 1024, "two workgroups per CU");
   __shared__ __attribute__((aligned(16))) char lds[GBYTES + ABYTES + WBYTES];
@@ -83,38 +96,132 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
   const int li = lane & 15, lg = lane >> 4;
   const int split = blockIdx.x;
 
-  // ---- the weight matrix, resident for the whole walk; LDS row q holds the channel the MFMA row order needs so
-  // that a lane ends up with 8 contiguous channels of one pixel per 32-channel group ----
-  for (int idx = tid; idx < CI * VPG; idx += NT) {
-    const int q = idx / VPG, v = idx % VPG;
-    const int ci = (q & ~31) + ((q & 15) >> 2) * 8 + ((q >> 4) & 1) * 4 + (q & 3);
-    *(V16*)(wl + q * WROW + v * 16) = *(const V16*)(a.wT + ((size_t)ci * CO + v * VEC) * ES);
-  }
   // a thread keeps one channel vector of each side for every tile: its coefficients live in registers
   const int vg = tid % VPG, va = tid % VPA;
   const bool from_rows = a.ref.rows != nullptr;
   const bool has_coef = a.coef != nullptr || from_rows, has_aff = AFF && a.in_scale != nullptr, in_relu = a.in_relu != 0;
-  float cA[VEC], cB[VEC], cC[VEC], sc[AFF ? VEC : 1], sh[AFF ? VEC : 1];
-  const float* ctab = a.coef;
-  if (from_rows) {
-    // scratch and table live in the (still unused) tile region; the helper ends with a barrier
-    static_assert(NT * 2 * 8 + 3 * CO * 4 <= GBYTES + ABYTES, "row-sum scratch fits the tiles");
-    float* tab = (float*)(lds + NT * 2 * 8);
-    hr_bnbwd_coef_from_rows<NT, CO>(a.ref, CO, (double*)lds, tab, blockIdx.x == 0);
-    ctab = tab;
-  }
+
+  // ---- requests: everything up to the first staged tile depends on kernel arguments only, so all of it is in flight
+  // before anything is waited for - the first tile, the weight matrix, the coefficient inputs (as in bwd_fused.hip) ----
+  V16 rz[XG], ry[XG], rx[XA];
+  // buffer descriptors over the tile's own pixels (a tensor may pass 4 GB, a tile does not): one 32-bit offset register
+  // per tensor side instead of an address pair per vector, and the pixels beyond the last one read zeros
+  auto load_tile = [&](int t) {
+    const int voffg = ((tid / VPG) * CO + vg * VEC) * ES, voffa = ((tid / VPA) * CI + va * VEC) * ES;
+    const long long p0 = (long long)t * TP, left = a.P - p0;
+    const int npx = left < TP ? (int)left : TP;
+    const auto rdz = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dz + p0 * (CO * ES)), 0, npx * CO * ES, 0x00020000);
+    const auto rdy = __builtin_amdgcn_make_buffer_rsrc((void*)((has_coef ? a.y : a.dz) + p0 * (CO * ES)), 0,
+                                                       has_coef ? npx * CO * ES : 0, 0x00020000);
+    const auto rdx = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + p0 * (CI * ES)), 0, npx * CI * ES, 0x00020000);
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    cA[j] = has_coef ? ctab[vg * VEC + j] : 1.f;
-    cB[j] = has_coef ? ctab[CO + vg * VEC + j] : 0.f;
-    cC[j] = has_coef ? ctab[2 * CO + vg * VEC + j] : 0.f;
-    if constexpr (AFF) {
-      sc[j] = has_aff ? a.in_scale[va * VEC + j] : 1.f;
-      sh[j] = has_aff ? a.in_shift[va * VEC + j] : 0.f;
+    for (int k = 0; k < XG; ++k) {
+      rz[k] = __builtin_amdgcn_raw_buffer_load_b128(rdz, voffg + k * (PSG * CO * ES), 0, 0);
+      ry[k] = __builtin_amdgcn_raw_buffer_load_b128(rdy, voffg + k * (PSG * CO * ES), 0, 0);   // (no coefficients: an empty descriptor, nothing is fetched)
+    }
+#pragma unroll
+    for (int k = 0; k < XA; ++k) rx[k] = __builtin_amdgcn_raw_buffer_load_b128(rdx, voffa + k * (PSA * CI * ES), 0, 0);
+  };
+  if constexpr (HOIST) {
+    if (split < a.total_tiles) load_tile(split);
+  }
+  // the weight matrix, resident for the whole walk; LDS row q holds the channel the MFMA row order needs so that a
+  // lane ends up with 8 contiguous channels of one pixel per 32-channel group
+  constexpr int XW = CI * VPG / NT;
+  static_assert(CI * VPG % NT == 0, "whole rounds of weight vectors");
+  V16 wv[XW];
+  {
+    const auto rdw = __builtin_amdgcn_make_buffer_rsrc((void*)a.wT, 0, CI * CO * ES, 0x00020000);
+#pragma unroll
+    for (int k = 0; k < XW; ++k) {
+      const int idx = tid + k * NT;
+      const int q = idx / VPG, v = idx % VPG;
+      const int ci = (q & ~31) + ((q & 15) >> 2) * 8 + ((q >> 4) & 1) * 4 + (q & 3);
+      wv[k] = __builtin_amdgcn_raw_buffer_load_b128(rdw, (ci * CO + v * VEC) * ES, 0, 0);
     }
   }
-
-  if (from_rows) __syncthreads();   // every thread has its coefficients: the table's LDS becomes tile space
+  HrBnBwdIssued bst;
+  if constexpr (HOIST) {
+    if (from_rows) hr_bnbwd_rows_issue<NT, CO>(a.ref, CO, blockIdx.x == 0, bst);
+  }
+  // the thread's coefficients, through descriptors that are empty when the operand is absent (zeros, no branch)
+  float cA[VEC], cB[VEC], cC[VEC], sc[AFF ? VEC : 1], sh[AFF ? VEC : 1];
+  if constexpr (HOIST) {
+    const bool hc = a.coef != nullptr;
+    const auto rdc = __builtin_amdgcn_make_buffer_rsrc((void*)(hc ? (const char*)a.coef : a.wT), 0, hc ? 3 * CO * 4 : 0, 0x00020000);
+    const auto rds = __builtin_amdgcn_make_buffer_rsrc((void*)(has_aff ? (const char*)a.in_scale : a.wT), 0, has_aff ? CI * 4 : 0, 0x00020000);
+    const auto rdh = __builtin_amdgcn_make_buffer_rsrc((void*)(has_aff ? (const char*)a.in_shift : a.wT), 0, has_aff ? CI * 4 : 0, 0x00020000);
+    V16 tA[2], tB[2], tC[2], tS[2], tH[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      tA[h] = __builtin_amdgcn_raw_buffer_load_b128(rdc, (vg * VEC + h * 4) * 4, 0, 0);
+      tB[h] = __builtin_amdgcn_raw_buffer_load_b128(rdc, (CO + vg * VEC + h * 4) * 4, 0, 0);
+      tC[h] = __builtin_amdgcn_raw_buffer_load_b128(rdc, (2 * CO + vg * VEC + h * 4) * 4, 0, 0);
+      if constexpr (AFF) {
+        tS[h] = __builtin_amdgcn_raw_buffer_load_b128(rds, (va * VEC + h * 4) * 4, 0, 0);
+        tH[h] = __builtin_amdgcn_raw_buffer_load_b128(rdh, (va * VEC + h * 4) * 4, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      v16_unpack<float>(tA[h], cA + h * 4);
+      v16_unpack<float>(tB[h], cB + h * 4);
+      v16_unpack<float>(tC[h], cC + h * 4);
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) cA[j] = hc ? cA[j] : 1.f;     // (cB, cC: zeros out of the empty descriptor)
+    if constexpr (AFF) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        v16_unpack<float>(tS[h], sc + h * 4);
+        v16_unpack<float>(tH[h], sh + h * 4);
+      }
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) sc[j] = has_aff ? sc[j] : 1.f;
+    }
+  }
+  // ---- the one wait ----
+  float* tab = (float*)(lds + NT * 2 * 8);
+  static_assert(NT * 2 * 8 + 3 * CO * 4 <= GBYTES + ABYTES, "row-sum scratch fits the tiles");
+  if constexpr (HOIST) {
+#pragma unroll
+    for (int k = 0; k < XW; ++k) {
+      const int idx = tid + k * NT;
+      *(V16*)(wl + (idx / VPG) * WROW + (idx % VPG) * 16) = wv[k];
+    }
+    // scratch and table live in the (still unused) tile region; the helper ends with a barrier
+    if (from_rows) hr_bnbwd_coef_finish<NT, CO>(a.ref, CO, bst, (double*)lds, tab, blockIdx.x == 0);
+  } else {
+    // (no registers to spare in this instantiation: weights stored as they arrive, then the coefficient build)
+#pragma unroll
+    for (int k = 0; k < XW; ++k) {
+      const int idx = tid + k * NT;
+      *(V16*)(wl + (idx / VPG) * WROW + (idx % VPG) * 16) = wv[k];
+    }
+    if (from_rows) hr_bnbwd_coef_from_rows<NT, CO>(a.ref, CO, (double*)lds, tab, blockIdx.x == 0);
+    const float* ctab = from_rows ? tab : a.coef;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      cA[j] = has_coef ? ctab[vg * VEC + j] : 1.f;
+      cB[j] = has_coef ? ctab[CO + vg * VEC + j] : 0.f;
+      cC[j] = has_coef ? ctab[2 * CO + vg * VEC + j] : 0.f;
+      if constexpr (AFF) {
+        sc[j] = has_aff ? a.in_scale[va * VEC + j] : 1.f;
+        sh[j] = has_aff ? a.in_shift[va * VEC + j] : 0.f;
+      }
+    }
+  }
+  if (from_rows) {
+    if constexpr (HOIST) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        cA[j] = tab[vg * VEC + j];
+        cB[j] = tab[CO + vg * VEC + j];
+        cC[j] = tab[2 * CO + vg * VEC + j];
+      }
+    }
+    __syncthreads();   // every thread has its coefficients: the table's LDS becomes tile space
+  }
   // weight gradient: this wave's co fragments x ci fragments; D: col (li) = ci, rows (lg*4+r) = co
   const int wco = wave % COSPLIT, wci = wave / COSPLIT;
   f32x4 accw[FCOW][FCIW];
@@ -139,21 +246,29 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
 
   for (int t = split; t < a.total_tiles; t += a.nsplit) {
     const long long p0 = (long long)t * TP;
-    // ---- stage: every load of the tile is issued before the first use ----
-    V16 rz[XG], ry[XG], rx[XA];
+    // ---- stage: the tile's loads are in flight already (the prologue's, or the previous tile's request) ----
+    V16 lz[XG], ly[XG], lx[XA];
+    if constexpr (HOIST) {
 #pragma unroll
-    for (int k = 0; k < XG; ++k) {
-      const long long p = p0 + tid / VPG + k * PSG;
-      const bool ok = p < a.P;
-      const size_t o = ok ? ((size_t)p * CO + vg * VEC) * ES : 0;
-      rz[k] = *(const V16*)(a.dz + o);
-      if (has_coef) ry[k] = *(const V16*)(a.y + o);
-    }
+      for (int k = 0; k < XG; ++k) { lz[k] = rz[k]; ly[k] = ry[k]; }
 #pragma unroll
-    for (int k = 0; k < XA; ++k) {
-      const long long p = p0 + tid / VPA + k * PSA;
-      const size_t o = p < a.P ? ((size_t)p * CI + va * VEC) * ES : 0;
-      rx[k] = *(const V16*)(a.x + o);
+      for (int k = 0; k < XA; ++k) lx[k] = rx[k];
+    } else {
+      // every load of the tile is issued before the first use
+#pragma unroll
+      for (int k = 0; k < XG; ++k) {
+        const long long p = p0 + tid / VPG + k * PSG;
+        const bool ok = p < a.P;
+        const size_t o = ok ? ((size_t)p * CO + vg * VEC) * ES : 0;
+        lz[k] = *(const V16*)(a.dz + o);
+        if (has_coef) ly[k] = *(const V16*)(a.y + o);
+      }
+#pragma unroll
+      for (int k = 0; k < XA; ++k) {
+        const long long p = p0 + tid / VPA + k * PSA;
+        const size_t o = p < a.P ? ((size_t)p * CI + va * VEC) * ES : 0;
+        lx[k] = *(const V16*)(a.x + o);
+      }
     }
     // epilogue operands of this wave's 16 pixels (MFMA layout: 8 channels per 32-channel group)
     const long long pe = p0 + wave * 16 + li;
@@ -173,11 +288,11 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
     for (int k = 0; k < XG; ++k) {
       const int pl = tid / VPG + k * PSG;
       const bool ok = p0 + pl < a.P;
-      V16 g = rz[k];
+      V16 g = lz[k];
       if (has_coef) {
         float fz[VEC], fy[VEC];
-        v16_unpack<T>(rz[k], fz);
-        v16_unpack<T>(ry[k], fy);
+        v16_unpack<T>(lz[k], fz);
+        v16_unpack<T>(ly[k], fy);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) fz[j] = fmaf(cA[j], fz[j], fmaf(cB[j], fy[j], cC[j]));
         g = v16_pack<T>(fz);
@@ -188,10 +303,10 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
     for (int k = 0; k < XA; ++k) {
       const int pl = tid / VPA + k * PSA;
       const bool ok = p0 + pl < a.P;
-      V16 v = rx[k];
+      V16 v = lx[k];
       if (has_aff || in_relu) {
         float f[VEC];
-        v16_unpack<T>(rx[k], f);
+        v16_unpack<T>(lx[k], f);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           if constexpr (AFF) f[j] = fmaf(f[j], sc[j], sh[j]);
@@ -202,6 +317,10 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
       *(V16*)(al + pl * APIX + va * 16) = ok ? v : v16_zero();
     }
     __syncthreads();
+    const bool has_next = t + a.nsplit < a.total_tiles;
+    if constexpr (PREFETCH) {
+      if (has_next) load_tile(t + a.nsplit);     // issued early, written late: in flight under the matrix phases
+    }
 
     // ---- input gradient ----
     f32x4 accd[FCI];
@@ -301,6 +420,9 @@ __global__ __launch_bounds__(256, (CI > 64 ? 1 : 2)) void bwd_pw_kernel(PwArgs a
       }
     }
     __syncthreads();   // the tiles are free again
+    if constexpr (HOIST && !PREFETCH) {
+      if (has_next) load_tile(t + a.nsplit);
+    }
   }
 
   // ---- backward statistics: lanes -> waves -> one row per workgroup (deterministic) ----

@@ -189,18 +189,67 @@ __device__ __forceinline__ void hr_bn_from_sums(const float* sums, int C, int c,
 // (HrBnBwdRef): thread t sums rows t/CP, t/CP + NT/CP, ... of channel t%CP in f64, the row groups are added in a
 // fixed order, then A,B,C as hrnet_bn_bwd_finalize computes them. `scratch`: NT*2 doubles of LDS; `tab`: [3][CP]
 // floats of LDS. Ends with a barrier: tab is readable, scratch is free. `writer`: this workgroup stores dgamma/dbeta.
+//
+// Two halves, so that a kernel can put the loads of the first half in flight together with its own first loads and
+// pay one memory round trip for all of them: hr_bnbwd_rows_issue requests the thread's first HR_BNBWD_UB rows and the
+// per-channel values (no barrier, no LDS), hr_bnbwd_coef_finish does the rest. The rows are fetched UB at a time, every
+// load of a batch issued before the first add that consumes one (a loop of load, add waits out the latency of each
+// row - DESIGN section 4, trap 5); the adds themselves keep the order rg, rg + NRG, ... per thread.
+constexpr int HR_BNBWD_UB = 8;
+struct HrBnBwdIssued {
+  float r1[HR_BNBWD_UB], r2[HR_BNBWD_UB];   // rows rg, rg + NRG, ... of this thread's channel: (sum dz, sum dz * y)
+  float mu, iv, g, dg0, db0;                // per-channel values of the threads that finish a channel (tid < CP)
+};
+
+// the loads of rows t0, t0 + NRG, ... through a buffer descriptor over the rows (at most 16384 x 2 floats: 32-bit
+// offsets, one address register per load): an absent row or channel gets an offset beyond it - nothing is fetched, the
+// value is zero and its add is predicated off anyway
+template <int NRG>
+__device__ __forceinline__ void hr_bnbwd_rows_load(const HrBnBwdRef& r, int C, int c, int t0, float* r1, float* r2) {
+  const auto rd = __builtin_amdgcn_make_buffer_rsrc((void*)r.rows, 0, r.nrows * 2 * C * 4, 0x00020000);
+#pragma unroll
+  for (int u = 0; u < HR_BNBWD_UB; ++u) {
+    const int t = t0 + u * NRG;
+    const unsigned o = c < C && t < r.nrows ? (unsigned)((t * 2 * C + c) * 4) : 0x80000000u;
+    r1[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, o, 0, 0));
+    r2[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, o + (unsigned)(C * 4), 0, 0));
+  }
+}
+
 template <int NT, int CP>
-__device__ __forceinline__ void hr_bnbwd_coef_from_rows(const HrBnBwdRef& r, int C, double* scratch, float* tab,
-                                                        bool writer) {
+__device__ __forceinline__ void hr_bnbwd_rows_issue(const HrBnBwdRef& r, int C, bool writer, HrBnBwdIssued& st) {
   static_assert(NT % CP == 0, "row groups");
   constexpr int NRG = NT / CP;
   const int tid = threadIdx.x, c = tid % CP, rg = tid / CP;
-  double a = 0.0, b = 0.0;
-  if (c < C)
-    for (int t = rg; t < r.nrows; t += NRG) {
-      a += (double)r.rows[((size_t)t * 2 + 0) * C + c];
-      b += (double)r.rows[((size_t)t * 2 + 1) * C + c];
+  hr_bnbwd_rows_load<NRG>(r, C, c, rg, st.r1, st.r2);
+  st.mu = st.iv = st.g = st.dg0 = st.db0 = 0.f;
+  if (tid < CP && c < C) {
+    st.mu = r.save_mean[c];
+    st.iv = r.save_invstd[c];
+    st.g = r.gamma[c];
+    if (writer && r.accumulate) {
+      st.dg0 = r.dgamma[c];
+      st.db0 = r.dbeta[c];
     }
+  }
+}
+
+template <int NT, int CP>
+__device__ __forceinline__ void hr_bnbwd_coef_finish(const HrBnBwdRef& r, int C, HrBnBwdIssued& st, double* scratch,
+                                                     float* tab, bool writer) {
+  constexpr int NRG = NT / CP;
+  const int tid = threadIdx.x, c = tid % CP, rg = tid / CP;
+  double a = 0.0, b = 0.0;
+  for (int t0 = rg; t0 < r.nrows; t0 += HR_BNBWD_UB * NRG) {
+    if (t0 != rg) hr_bnbwd_rows_load<NRG>(r, C, c, t0, st.r1, st.r2);
+#pragma unroll
+    for (int u = 0; u < HR_BNBWD_UB; ++u) {
+      if (c < C && t0 + u * NRG < r.nrows) {
+        a += (double)st.r1[u];
+        b += (double)st.r2[u];
+      }
+    }
+  }
   scratch[(rg * 2 + 0) * CP + c] = a;
   scratch[(rg * 2 + 1) * CP + c] = b;
   __syncthreads();
@@ -208,15 +257,16 @@ __device__ __forceinline__ void hr_bnbwd_coef_from_rows(const HrBnBwdRef& r, int
     float A = 0.f, B = 0.f, Cc = 0.f;
     if (c < C) {
       double s1 = 0.0, s2 = 0.0;
+#pragma unroll
       for (int q = 0; q < NRG; ++q) {
         s1 += scratch[(q * 2 + 0) * CP + c];
         s2 += scratch[(q * 2 + 1) * CP + c];
       }
-      const double mu = r.save_mean[c], iv = r.save_invstd[c], g = r.gamma[c], n = (double)r.count;
+      const double mu = st.mu, iv = st.iv, g = st.g, n = (double)r.count;
       const double dg = iv * (s2 - mu * s1);   // sum dz * xhat
       if (writer) {
-        r.dgamma[c] = r.accumulate ? r.dgamma[c] + (float)dg : (float)dg;
-        r.dbeta[c] = r.accumulate ? r.dbeta[c] + (float)s1 : (float)s1;
+        r.dgamma[c] = r.accumulate ? st.dg0 + (float)dg : (float)dg;
+        r.dbeta[c] = r.accumulate ? st.db0 + (float)s1 : (float)s1;
       }
       A = (float)(g * iv);
       B = (float)(-g * iv * iv * dg / n);
@@ -227,6 +277,14 @@ __device__ __forceinline__ void hr_bnbwd_coef_from_rows(const HrBnBwdRef& r, int
     tab[2 * CP + c] = Cc;
   }
   __syncthreads();
+}
+
+template <int NT, int CP>
+__device__ __forceinline__ void hr_bnbwd_coef_from_rows(const HrBnBwdRef& r, int C, double* scratch, float* tab,
+                                                        bool writer) {
+  HrBnBwdIssued st;
+  hr_bnbwd_rows_issue<NT, CP>(r, C, writer, st);
+  hr_bnbwd_coef_finish<NT, CP>(r, C, st, scratch, tab, writer);
 }
 
 // host-side error plumbing (api.hip)
