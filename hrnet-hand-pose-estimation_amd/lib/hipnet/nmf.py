@@ -187,9 +187,12 @@ def reconstruct(bases, coef, out):
     return out
 
 
-def factorise(x, bases, steps, out):
+def factorise(x, bases, steps, out, keep=False):
     """the iteration of NMF2D in eval mode (ham.py:49-58, :244-269, :93) on x (G, D, N), bases (G, D, R), both as above;
-    the reconstruction goes to the view `out` (G, D, N). 3 + 4 steps + 2 launches, plus one per split Gram matrix."""
+    the reconstruction goes to the view `out` (G, D, N). 3 + 4 steps + 2 launches, plus one per split Gram matrix.
+    keep: return (out, (bases_T, coef_T, Gm)) - the factors after `steps` updates, BEFORE the closing coefficient update,
+    and Gm = bases_T^T bases_T: what the one-step gradient of hipnet.nmf_train reads (the closing update writes to the
+    spare buffer, so coef_T is intact; with steps = 0 bases_T is the caller's tensor)."""
     G, D, N = x.shape
     R = bases.shape[2]
     dev = x.device
@@ -202,8 +205,9 @@ def factorise(x, bases, steps, out):
     for k in range(int(steps)):
         coef, spare_c = update_coef(coef, bases, x, gram(bases, gm, scratch), spare_c), coef
         bases = update_bases(bases, coef, x, gram(coef, gm, scratch), own[k % 2])
-    coef = update_coef(coef, bases, x, gram(bases, gm, scratch), spare_c)
-    return reconstruct(bases, coef, out)
+    last = update_coef(coef, bases, x, gram(bases, gm, scratch), spare_c)
+    reconstruct(bases, last, out)
+    return (out, (bases, coef, gm)) if keep else out
 
 
 def group_view(name, x, spatial, S):
@@ -229,6 +233,16 @@ def group_view(name, x, spatial, S):
     return [(b * S, x.as_strided((S,) + size, (Dc * sc,) + strides, x.storage_offset() + b * sb)) for b in range(B)]
 
 
+def paired_views(name, a, b, spatial, S):
+    """group_view of two tensors of one shape, cut alike: when one is evenly spaced and the other is not, both go image
+    by image"""
+    va, vb = group_view(name, a, spatial, S), group_view(name, b, spatial, S)
+    if len(va) != len(vb):
+        per = lambda t: [(i * int(S), v) for i in range(t.shape[0]) for _, v in group_view(name, t[i:i + 1], spatial, S)]
+        va, vb = per(a), per(b)
+    return va, vb
+
+
 def nmf2d(x, bases, steps, spatial, S, out=None):
     """NMF2D in eval mode on given bases: x (B, C, H, W), any strides (NCHW, channels-last, a channel slice), non-negative;
     bases (B * S, D, R) with D = C / S (spatial) or H * W (not), already normalised; steps = EVAL_STEPS. Returns the
@@ -246,10 +260,7 @@ def nmf2d(x, bases, steps, spatial, S, out=None):
         out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
     elif tuple(out.shape) != tuple(x.shape):
         raise ValueError('nmf2d: out {}: expected x\'s shape {}'.format(tuple(out.shape), tuple(x.shape)))
-    outs = group_view('nmf2d', out, spatial, S)
-    if len(outs) != len(xs):                 # one of the two is evenly spaced, the other is not: go image by image
-        per = lambda t: [(b * int(S), v) for b in range(t.shape[0]) for _, v in group_view('nmf2d', t[b:b + 1], spatial, S)]
-        xs, outs = per(x), per(out)
+    xs, outs = paired_views('nmf2d', x, out, spatial, S)
     bases = bases.detach().contiguous()
     for (g0, xv), (_, ov) in zip(xs, outs):
         factorise(xv.detach(), bases[g0:g0 + xv.shape[0]], steps, ov)

@@ -1,7 +1,8 @@
 """HamNet, MODEL.NAME `pose_hrnet_hamburger` (reference lib/models/pose_hrnet_hamburger.py:17-84 with
 lib/models/hamburger/burger.py:123-201 HamburgerV2Plus, ham.py:14-117, :227-269 NMF2D and bread.py:20-49): a Hamburger
 block - a non-negative matrix factorisation of the feature map between two 1x1 convolutions - on the 480-channel features
-of pose_hrnet_softmax, and a spatial softmax. Inference only.
+of pose_hrnet_softmax, and a spatial softmax. HamNet(cfg) is inference only; HamNet(cfg, is_train, trainable=True) also
+trains its head (TRAINING below).
 
 forward(x): x (B, 3, H, W)
   1. backbone -> features (B, 480, h, w) (slot 1 of pose_hrnet_softmax's output)                         hamburger.py:69
@@ -45,18 +46,42 @@ used.
 Refused when the model is built, each naming its key: MODEL.HAM_TYPE other than 'NMF' (VQ and CD are not built),
 MODEL.VERSION other than 'V2+', MODEL.RAND_INIT false (the persistent bases buffer and its online update), a
 MODEL.BACKBONE_NAME without 'hrnet' (the ResNet backbone), MODEL.COMPUTE_DTYPE other than fp32, an S, R, EMB_DIM,
-CHEESE_FACTOR or EVAL_STEPS that does not fit. Refused in forward: CPU tensors (ValueError); training mode, and eval mode
-with a gradient required (NotImplementedError: SyncBN batch statistics, the backward through the last coefficient update
-and Dropout2d are not built - run model.eval() under torch.no_grad()).
+CHEESE_FACTOR or EVAL_STEPS that does not fit. Refused in forward: CPU tensors (ValueError); without trainable=True training
+mode, and in every model eval mode with a gradient required (NotImplementedError - run model.eval() under
+torch.no_grad()).
+
+TRAINING (trainable=True; tools/train_hamburger.py). In training mode head_forward(features, bases=None, drop_keep=None)
+runs under autograd on hipnet.burger_train and hipnet.nmf_train: squeeze, lower_bread, the hams on MODEL.TRAIN_STEPS with
+the bases drawn as above, cheese, upper_bread, the mix relu(coef_ham x + coef_shortcut shortcut) (hrnet_burger_mix: its
+backward forms both map gradients and the two scalar ones in one pass, the sums in double in a fixed order), align,
+Dropout2d(0.1) on the keep mask of draw_drop_keep (hrnet_dropout2d), fc and the spatial softmax. Every activation is
+materialised; the BatchNorms run on batch statistics and move their running ones with momentum 3e-4 through their
+pointers (so the packed plan is dropped after a training forward; num_batches_tracked is NOT incremented: the
+reference's SyncBN calls F.batch_norm directly and its counter stays 0); the packed weights are rebuilt on every call.
+  The ham's gradient needs no kernel of its own: the reference runs the TRAIN_STEPS updates under torch.no_grad()
+(ham.py:48-58), so only compute_coef and the closing bmm carry one (ham.py:90-93, :261-269). With bases_T, coef_T the
+factors after TRAIN_STEPS updates and Gm = bases_T^T bases_T: dnum = coef_T * (dY^T bases_T) / (coef_T Gm + 1e-6) is
+hrnet_nmf_update with dY where X sits, dX = bases_T dnum^T is hrnet_nmf_reconstruct into the gradient's own strided view
+(1.4e-16 of max|dX| against autograd through the reference's NMF2D in float64). A single fused launch would save one
+(G, N, R) round trip, 8 MB at full size, against about 6 GFLOP of products, and was not built. The bases get no gradient.
+  The backbone keeps every parameter frozen and runs under torch.no_grad() in whatever mode the module is in: no
+gradient enters it and its parameters never get a .grad, but model.train() puts its BatchNorms on batch statistics, as
+in the reference (which freezes the parameters and leaves the mode alone). features.requires_grad is honoured by
+head_forward: squeeze then forms its input gradient. Eval mode under no_grad is the inference path above, on EVAL_STEPS
+and on the statistics that training left. WORLD_SIZE > 1 is refused when the trainable model is built.
 """
 import logging
+import os
 
 import torch
 import torch.nn as nn
 
 from hipnet import _capi as C
+from hipnet import burger_train as BT
 from hipnet import nmf as N
+from hipnet import nmf_train as NT
 from hipnet import swin as S
+from hipnet import swin_train as ST
 
 logger = logging.getLogger(__name__)
 
@@ -231,10 +256,19 @@ def _fold(bn):
 
 
 class HamNet(nn.Module):
-    def __init__(self, config, is_train=False):
+    autograd_grads = True      # a trainable model's gradients are autograd .grad tensors (utils.get_optimizer)
+
+    def __init__(self, config, is_train=False, trainable=False):
         super(HamNet, self).__init__()
         check_config(config)
         M = config.MODEL
+        self.trainable = bool(trainable)
+        if self.trainable and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            raise ValueError('HamNet(trainable=True): WORLD_SIZE = {}: data-parallel training of pose_hrnet_hamburger is '
+                             'not built'.format(os.environ['WORLD_SIZE']))
+        if self.trainable and int(M.TRAIN_STEPS) < 0:
+            raise ValueError('MODEL.TRAIN_STEPS {}: must be at least 0'.format(M.TRAIN_STEPS))
+        self.train_steps = int(M.TRAIN_STEPS)
         # own parameters precede the sub-modules in a state dict, as the reference's lists them
         self.trainable_temp = nn.Parameter(torch.tensor(1.0), requires_grad=bool(M.TRAINABLE_SOFTMAX))
         from models import pose_hrnet_softmax
@@ -297,6 +331,13 @@ class HamNet(nn.Module):
 
     # ---- the model -------------------------------------------------------------------------------------------------
     def _refuse(self, x):
+        if self.training and self.trainable:
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise ValueError('HamNet: expected HIP-device tensors (there is no CPU path in this build)')
+            if self.trainable_temp.device != x.device:
+                raise ValueError('HamNet: the model is on {} and the input on {}: move the model with .cuda()'.format(
+                    self.trainable_temp.device, x.device))
+            return
         if self.training:
             raise NotImplementedError('HamNet: {} (SyncBN batch statistics, the backward through the last coefficient '
                                       'update and Dropout2d are a later step): call .eval() and run under '
@@ -311,9 +352,48 @@ class HamNet(nn.Module):
             raise ValueError('HamNet: the model is on {} and the input on {}: move the model with .cuda()'.format(
                 self.trainable_temp.device, x.device))
 
-    def head_forward(self, features, bases=None):
+    # ---- training (trainable=True) ---------------------------------------------------------------------------------
+    def draw_drop_keep(self, B, device):
+        """the keep mask of fc's Dropout2d(0.1): (B, 256) values in {0, 1 / 0.9}, drawn on the device from torch's
+        generator"""
+        p = float(self.fc[0].p)
+        return torch.empty((B, ALIGN_CHANNELS), dtype=torch.float32, device=device).bernoulli_(1.0 - p).div_(1.0 - p)
+
+    def _head_train(self, features, bases, drop_keep):
+        """head_forward in training mode under autograd, on hipnet.burger_train and hipnet.nmf_train: every activation is
+        materialised, the BatchNorms run on batch statistics and update their running ones (num_batches_tracked stays),
+        the packed weights are rebuilt from the parameters on every call"""
+        from models.pose_hrnet_softmax import _SpatialSoftmax
+        B, _, hh, ww = features.shape
+        dev = features.device
+        if drop_keep is None:
+            drop_keep = self.draw_drop_keep(B, dev)
+        if not isinstance(drop_keep, torch.Tensor) or tuple(drop_keep.shape) != (B, ALIGN_CHANNELS):
+            raise ValueError('drop_keep {}: expected ({}, {})'.format(tuple(getattr(drop_keep, 'shape', ())), B,
+                                                                      ALIGN_CHANNELS))
+        h = self.hamburger
+        keep = torch.zeros((B, S.pad16(ALIGN_CHANNELS)), dtype=torch.float32, device=dev)
+        keep[:, :ALIGN_CHANNELS] = drop_keep.to(device=dev, dtype=torch.float32)
+        with torch.no_grad():
+            nb = [N.normalise_bases(b.to(device=dev, dtype=torch.float32)) for b in bases]
+        specs = [(ham.spatial, c0, ch, ham.S) for ham, c0, ch in h.hams()]
+        x = BT.to_nhwc(features.float(), S.pad16(self.in_channel))
+        sq = BT.conv_bn_relu_train(x, self.squeeze.conv, self.squeeze.bn, 3)
+        low = BT.conv1x1_train(sq, h.lower_bread[0], relu_out=True)
+        y = NT.hams_train(low, specs, nb, self.train_steps)
+        y = BT.conv_bn_relu_train(y, h.cheese.conv, h.cheese.bn, 1)
+        y = BT.conv1x1_train(y, h.upper_bread)
+        y = BT.burger_mix(y, sq, h.coef_ham, h.coef_shortcut)
+        y = BT.conv_bn_relu_train(y, self.align.conv, self.align.bn, 3)
+        y = BT.conv1x1_train(BT.dropout2d(y, keep), self.fc[1])
+        self._plan = None                 # the running statistics were written through their pointers, not their version
+        return _SpatialSoftmax.apply(ST.to_nchw(y, self.num_joints), self.trainable_temp)
+
+    def head_forward(self, features, bases=None, drop_keep=None):
         """features (B, 480, h, w) NCHW on the device -> heat maps: everything after the backbone. bases: None (drawn here
-        as the reference draws them), or a list of one tensor per ham, (B * S, D, R), NOT yet normalised (CPU or device)"""
+        as the reference draws them), or a list of one tensor per ham, (B * S, D, R), NOT yet normalised (CPU or device).
+        In training mode of a trainable model the hams run MODEL.TRAIN_STEPS steps and drop_keep is the (B, 256) keep mask
+        of draw_drop_keep (None: drawn here); features.requires_grad is honoured"""
         self._refuse(features)
         if features.ndim != 4 or features.shape[1] != self.in_channel or features.numel() == 0:
             raise ValueError('features {}: expected (B, {}, h, w)'.format(tuple(features.shape), self.in_channel))
@@ -324,6 +404,10 @@ class HamNet(nn.Module):
         bases = list(bases) if isinstance(bases, (list, tuple)) else [bases]
         if len(bases) != len(shapes) or any(tuple(b.shape) != s for b, s in zip(bases, shapes)):
             raise ValueError('bases {}: expected {}'.format([tuple(b.shape) for b in bases], shapes))
+        if self.training:
+            return self._head_train(features, bases, drop_keep)
+        if drop_keep is not None:
+            raise ValueError('drop_keep is for training mode')
         with torch.no_grad():
             p = self._head_plan()
             dev = features.device
@@ -352,11 +436,11 @@ class HamNet(nn.Module):
             y = conv_nhwc(y, p['w_fc'], p['jp'], 1, bias=p['b_fc'], in_affine=p['bn_align'], in_relu=True)
             return S.heatmap_softmax(y, self.num_joints, self.trainable_temp)
 
-    def forward(self, x, bases=None):
+    def forward(self, x, bases=None, drop_keep=None):
         self._refuse(x)
-        with torch.no_grad():
+        with torch.no_grad():            # frozen: no parameter of the backbone requires a gradient, in any mode
             features = self.backbone(x)[1]
-        return self.head_forward(features, bases), self.trainable_temp
+        return self.head_forward(features, bases, drop_keep), self.trainable_temp
 
 
 def get_pose_net(cfg, is_train, **kwargs):

@@ -1176,6 +1176,35 @@ int hrnet_nmf_reconstruct(const float* Bs, const float* Cf, float* out, long lon
                           int N, int R, hr_stream_t stream);
 
 /*
+ * The burger's glue of pose_hrnet_hamburger in training mode (csrc/burger_train.hip; reference
+ * lib/models/hamburger/burger.py:198-199 and the Dropout2d of lib/models/pose_hrnet_hamburger.py:62). Streaming kernels:
+ * f32, NHWC rows [rows][C], C % 16 == 0, 64-bit element offsets (rows * C <= 2^40), pad channels zero on the way in and
+ * kept zero on the way out. Stream-ordered, no allocation, no host synchronisation, NO atomics. Every argument check
+ * (HR_E_BADARG) comes before the first launch. The grid is a fixed number of workgroups, a function of the shape alone,
+ * that strides over the map; 16-byte accesses when every map pointer is 16-byte aligned, element-wise accesses in the same
+ * kernel otherwise. The ham's own gradient needs no entry here: it is hrnet_nmf_update with dY where X sits, then
+ * hrnet_nmf_reconstruct (lib/hipnet/nmf_train.py).
+ *
+ * burger_mix: out = relu(*coef_ham * u + *coef_shortcut * s). The two coefficients are device scalars: nothing is read on
+ *   the host. out may be u itself (not s).
+ * burger_mix_scratch: pure host query: the doubles of scratch the backward needs for this shape, 0 for a shape it refuses.
+ * burger_mix_bwd: ONE pass over the maps. With gm = g where out > 0, else 0: du = *coef_ham * gm, ds = *coef_shortcut * gm
+ *   (both WRITTEN; a caller that has more to add to ds accumulates into it afterwards, hrnet_conv2d's accumulate flag),
+ *   dcoef[0] = sum gm * u, dcoef[1] = sum gm * s as floats. The sums are made in double: per thread, then per workgroup in
+ *   a fixed order into scratch [workgroups][2], which a second launch adds in index order - a call is bit-reproducible.
+ *   du may be g itself. du, ds, dcoef: NULL = not formed (at least one is given); scratch may be NULL when dcoef is.
+ * dropout2d: y[b, p, c] = x[b, p, c] * keep[b * C + c], x and y [B][P][C], keep [B][C]: Dropout2d with the mask given (keep
+ *   holds 0 or 1 / (1 - p)). y may be x itself. The same entry is its own backward (dx = dy * keep).
+ */
+int hrnet_burger_mix(const float* u, const float* s, const float* coef_ham, const float* coef_shortcut, float* out,
+                     long long rows, int C, hr_stream_t stream);
+hr_value_t hrnet_burger_mix_scratch(long long rows, int C);
+int hrnet_burger_mix_bwd(const float* g, const float* out, const float* u, const float* s, const float* coef_ham,
+                         const float* coef_shortcut, float* du, float* ds, float* dcoef, double* scratch,
+                         long long scratch_doubles, long long rows, int C, hr_stream_t stream);
+int hrnet_dropout2d(const float* x, const float* keep, float* y, int B, long long P, int C, hr_stream_t stream);
+
+/*
  * Spatial softmax head of pose_hrnet_softmax (lib/models/pose_hrnet_softmax.py:520-524):
  * out[bk, :] = softmax(x[bk, :] * *temp) over the HW positions of each map, NCHW f32.
  * backward: dx = temp * out * (gout - sum(gout*out)); dtemp_partial[bk] = sum_i dz_i * x_i with
