@@ -5,54 +5,40 @@ pose_hrnet_PoseAggr in TRAINING mode (reference lib/models/pose_hrnet_PoseAggr.p
 Activations are NHWC tensors in the compute dtype (channel counts padded as the kernels need: multiples of 8 in,
 16 out); parameters stay the module's f32 OIHW tensors and are packed per call (these paths are small and not
 performance critical). Every forward / backward below is a hrnet_* launch; torch supplies memory, views and the
-autograd graph only.
+autograd graph only. Weight packing, the plain convolution, the whole-kernel weight gradient and the nine-tap 3x3 go
+through the launchers of hipnet.nhwc, whose ToNHWC / ToNCHW are the layout Functions of these paths too; what stays here
+runs on the recorded kernels' row-sum BatchNorm (ConvBN), or is this head's own (AddReLU, the tap-by-tap weight gradient
+of DilatedConv, LinComb).
 """
 import ctypes
 
 import torch
 
 from . import _capi as C
+from . import nhwc
 from . import ops
 
 
 def _dt(t):
-    return 0 if t.dtype == torch.float32 else 1
+    return C.dtype_id(t.dtype)
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
+def _pads(w):
+    """the padded (Cout, Cin) of an OIHW weight here: multiples of 16 and of 8"""
+    return (w.shape[0] + 15) // 16 * 16, (w.shape[1] + 7) // 8 * 8
 
 
 def _pack(w, dtype, mode, ks):
     """OIHW f32 -> packed kernel layout (mode 0 forward / 1 transposed input-gradient copy)"""
-    co, ci = w.shape[0], w.shape[1]
-    cop, cip = (co + 15) // 16 * 16, (ci + 7) // 8 * 8
-    out = torch.empty(cop * ks * ks * cip, dtype=dtype, device=w.device)
+    cop, cip = _pads(w)
     wf = w.detach().float().contiguous()
-    C.call('hrnet_pack_weights', 0 if dtype == torch.float32 else 1, wf.data_ptr(), out.data_ptr(), co, ci, ks, cop, cip,
-           mode, C.stream_ptr())
-    return out, cop, cip
+    return nhwc.pack(wf, w.shape[0], w.shape[1], ks, cop, cip, mode, C.dtype_id(dtype)), cop, cip
 
 
 def _conv_backward(x, gy, weight, ks, need_gx):
     """input gradient (conv with the transposed packed kernel) and weight gradient (slabs + reduce) of y = conv(x)"""
-    N, H, W, cin = x.shape
-    cout = gy.shape[3]
-    dt = _dt(x)
-    gx = None
-    if need_gx:
-        wd, _, _ = _pack(weight, x.dtype, 1, ks)
-        gx = torch.empty_like(x)
-        C.call('hrnet_conv2d', dt, gy.data_ptr(), wd.data_ptr(), None, None, None, gx.data_ptr(), None, N, H, W, cout,
-               H, W, cin, ks, 1, 0, 0, 0, C.stream_ptr())
-    ns = C.call('hrnet_wgrad_splits', dt, N, H, W, cout, cin, ks, 1)
-    slabs = torch.empty(ns * cout * ks * ks * cin, dtype=torch.float32, device=x.device)
-    C.call('hrnet_conv2d_wgrad', dt, x.data_ptr(), gy.data_ptr(), None, None, slabs.data_ptr(), N, H, W, cin, H, W,
-           cout, ks, 1, 0, ns, C.stream_ptr())
-    gw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
-    C.call('hrnet_wgrad_reduce', slabs.data_ptr(), gw.data_ptr(), ns, cout, cin, ks, weight.shape[0], weight.shape[1],
-           0, 0, C.stream_ptr())
-    return gx, gw
+    gx = nhwc.conv(gy, _pack(weight, x.dtype, 1, ks)[0], x.shape[3], ks, dtype=_dt(x)) if need_gx else None
+    return gx, nhwc.wgrad(x, gy, ks, 1, weight.shape[0], weight.shape[1])
 
 
 class ConvBN(torch.autograd.Function):
@@ -130,59 +116,6 @@ class AddReLU(torch.autograd.Function):
         return d, d
 
 
-class ToNHWC(torch.autograd.Function):
-    """NCHW f32 -> NHWC compute dtype, channels zero-padded to cpad"""
-
-    @staticmethod
-    def forward(ctx, x, cpad, dtype):
-        N, c, H, W = x.shape
-        out = torch.empty((N, H, W, cpad), dtype=dtype, device=x.device)
-        C.call('hrnet_nchw_to_nhwc', 0 if dtype == torch.float32 else 1, x.contiguous().data_ptr(), out.data_ptr(), N, H, W,
-               cpad, c, C.stream_ptr())
-        ctx.c = c
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        N, H, W, cpad = g.shape
-        out = torch.empty((N, ctx.c, H, W), dtype=torch.float32, device=g.device)
-        C.call('hrnet_nhwc_to_nchw', _dt(g), g.contiguous().data_ptr(), out.data_ptr(), N, H, W, cpad, ctx.c, C.stream_ptr())
-        return out, None, None
-
-
-class ToNCHW(torch.autograd.Function):
-    """NHWC compute dtype -> NCHW f32, first c channels"""
-
-    @staticmethod
-    def forward(ctx, x, c):
-        N, H, W, cpad = x.shape
-        out = torch.empty((N, c, H, W), dtype=torch.float32, device=x.device)
-        C.call('hrnet_nhwc_to_nchw', _dt(x), x.contiguous().data_ptr(), out.data_ptr(), N, H, W, cpad, c, C.stream_ptr())
-        ctx.cpad, ctx.dtype = cpad, x.dtype
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        N, c, H, W = g.shape
-        out = torch.empty((N, H, W, ctx.cpad), dtype=ctx.dtype, device=g.device)
-        C.call('hrnet_nchw_to_nhwc', 0 if ctx.dtype == torch.float32 else 1, g.contiguous().float().data_ptr(),
-               out.data_ptr(), N, H, W, ctx.cpad, c, C.stream_ptr())
-        return out, None
-
-
-def _tap_matrices(weight, dtype, transposed):
-    """the nine 1x1 matrices of a 3x3 kernel, packed; transposed: [Cin][Cout] of the mirrored tap (input gradient)"""
-    w = weight.detach().float()
-    mats = []
-    for t in range(9):
-        src = 8 - t if transposed else t
-        m = w[:, :, src // 3, src % 3]
-        m = (m.t() if transposed else m).contiguous().reshape(m.shape[1] if transposed else m.shape[0], -1, 1, 1)
-        mats.append(_pack(m, dtype, 0, 1))
-    cop, cip = mats[0][1], mats[0][2]
-    return torch.stack([m[0] for m in mats]), cop, cip
-
-
 class DilatedConv(torch.autograd.Function):
     """y = conv3x3(x, dilation d, padding d), no bias (the offset convs, pose_hrnet_PoseAggr.py:497-506).
     backward: the input gradient is the same op with the transposed, mirrored taps; the weight gradient of tap t
@@ -190,12 +123,11 @@ class DilatedConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, dilation):
-        N, H, W, cin = x.shape
-        taps, cop, cip = _tap_matrices(weight, x.dtype, False)
-        assert cip == cin
-        y = torch.empty((N, H, W, cop), dtype=x.dtype, device=x.device)
-        C.call('hrnet_conv2d_dilated3x3', _dt(x), x.data_ptr(), taps.data_ptr(), taps.stride(0) * taps.element_size(),
-               y.data_ptr(), N, H, W, cin, cop, dilation, C.stream_ptr())
+        co, ci = weight.shape[:2]
+        cop, cip = _pads(weight)
+        assert cip == x.shape[3]
+        y = nhwc.conv3x3_taps(x, nhwc.pack_taps(weight.detach().float().contiguous(), co, ci, cop, cip, 0, _dt(x)), cop,
+                              dilation)
         ctx.save_for_backward(x, weight)
         ctx.d = dilation
         return y
@@ -209,14 +141,11 @@ class DilatedConv(torch.autograd.Function):
         gy = gy.contiguous()
         gx = None
         if ctx.needs_input_grad[0]:
-            # (padded output channels of y carry zero weights: pad the transposed matrices' K to cop)
-            w = weight.detach().float()
-            wpad = torch.zeros((cop, cin, 3, 3), dtype=torch.float32, device=x.device)
-            wpad[:w.shape[0], :w.shape[1]] = w
-            taps_t, _, _ = _tap_matrices(wpad, x.dtype, True)
-            gx = torch.empty_like(x)
-            C.call('hrnet_conv2d_dilated3x3', dt, gy.data_ptr(), taps_t.data_ptr(), taps_t.stride(0) * taps_t.element_size(),
-                   gx.data_ptr(), N, H, W, cop, cin, d, C.stream_ptr())
+            # (padded output channels of y carry zero weights: the transposed matrices' K is cop; their rows are padded to
+            # a multiple of 16 as a packed Cout is)
+            taps_t = nhwc.pack_taps(weight.detach().float().contiguous(), weight.shape[0], weight.shape[1], cop,
+                                    nhwc.pad16(cin), 1, dt)
+            gx = nhwc.conv3x3_taps(gy, taps_t, cin, d)
         # weight gradient, tap by tap
         eye = torch.eye(cin, dtype=torch.float32, device=x.device).reshape(cin, cin, 1, 1)
         ident, _, _ = _pack(eye, x.dtype, 0, 1)

@@ -19,20 +19,11 @@ call. There is no autograd here: an input that requires grad while grad is enabl
 import torch
 
 from hipnet import _capi as C
+from hipnet.nhwc import check
 
 OP_UPDATE, OP_GRAM, OP_PRODUCT = (C.VALUES['HR_NMF_' + n] for n in ('UPDATE', 'GRAM', 'PRODUCT'))
 EPS = 1e-6                   # the reference's denominator guard (ham.py:250, :257, :267)
 MAX_G = 65535
-
-
-def _check(name, **tensors):
-    for k, t in tensors.items():
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError('{}: {} must be a HIP-device tensor (there is no CPU path in this build)'.format(name, k))
-        if t.dtype != torch.float32:
-            raise ValueError('{}: {} is {}: float32 only'.format(name, k, t.dtype))
 
 
 def _no_grad(name, *ts):
@@ -75,7 +66,7 @@ def _view(name, x):
 
 def product(x, bases):
     """x (G, D, N) strided, bases (G, D, R) -> X^T bases (G, N, R)"""
-    _check('product', x=x, bases=bases)
+    check('product', x=x, bases=bases)
     p, ld, bs, orient = _view('product', x)
     G, D, N = x.shape
     if bases.ndim != 3 or bases.shape[0] != G or bases.shape[1] != D or bases.shape[2] < 1:
@@ -91,7 +82,7 @@ def product(x, bases):
 
 def softmax_rows(z, out=None):
     """softmax over the last axis of z (G, N, R): hrnet_spatial_softmax_fwd on G * N rows with temperature 1"""
-    _check('softmax_rows', z=z, out=out)
+    check('softmax_rows', z=z, out=out)
     if z.ndim != 3 or z.numel() == 0 or z.shape[0] * z.shape[1] > 0x7fffffff:
         raise ValueError('softmax_rows: z {}: expected (G, N, R), nothing empty'.format(tuple(z.shape)))
     _no_grad('softmax_rows', z)
@@ -113,7 +104,7 @@ def gram_scratch(G, K, R):
 
 def gram(a, out=None, scratch=None):
     """a (G, K, R) -> a^T a (G, R, R); scratch: None (allocated here) or a float32 tensor of gram_scratch(G, K, R) values"""
-    _check('gram', a=a, out=out, scratch=scratch)
+    check('gram', a=a, out=out, scratch=scratch)
     if a.ndim != 3 or a.numel() == 0 or a.shape[0] > MAX_G or not supported(OP_GRAM, a.shape[1], a.shape[2]):
         raise ValueError('gram: a {}: expected (G, K, R), nothing empty, G <= {}'.format(tuple(a.shape), MAX_G))
     _no_grad('gram', a)
@@ -156,7 +147,7 @@ def _update(name, t, f, x, gm, xt_of, M, K, out, eps):
 
 def update_coef(coef, bases, x, gm, out=None, eps=EPS):
     """coef (G, N, R) * (X^T bases) / (coef gm + eps) with gm = bases^T bases (G, R, R)"""
-    _check('update_coef', coef=coef, bases=bases, x=x, gm=gm, out=out)
+    check('update_coef', coef=coef, bases=bases, x=x, gm=gm, out=out)
     _no_grad('update_coef', coef, bases, x, gm)
     if x.ndim != 3:
         raise ValueError('update_coef: x {}: expected (G, D, N)'.format(tuple(x.shape)))
@@ -165,7 +156,7 @@ def update_coef(coef, bases, x, gm, out=None, eps=EPS):
 
 def update_bases(bases, coef, x, gm, out=None, eps=EPS):
     """bases (G, D, R) * (X coef) / (bases gm + eps) with gm = coef^T coef (G, R, R)"""
-    _check('update_bases', bases=bases, coef=coef, x=x, gm=gm, out=out)
+    check('update_bases', bases=bases, coef=coef, x=x, gm=gm, out=out)
     _no_grad('update_bases', bases, coef, x, gm)
     if x.ndim != 3:
         raise ValueError('update_bases: x {}: expected (G, D, N)'.format(tuple(x.shape)))
@@ -174,7 +165,7 @@ def update_bases(bases, coef, x, gm, out=None, eps=EPS):
 
 def reconstruct(bases, coef, out):
     """out (G, D, N), a strided view as x is: out_g = bases_g coef_g^T, written in place; returns out"""
-    _check('reconstruct', bases=bases, coef=coef, out=out)
+    check('reconstruct', bases=bases, coef=coef, out=out)
     p, ld, bs, orient = _view('reconstruct', out)
     G, D, N = out.shape
     if bases.ndim != 3 or bases.shape[2] < 1:
@@ -247,7 +238,7 @@ def nmf2d(x, bases, steps, spatial, S, out=None):
     """NMF2D in eval mode on given bases: x (B, C, H, W), any strides (NCHW, channels-last, a channel slice), non-negative;
     bases (B * S, D, R) with D = C / S (spatial) or H * W (not), already normalised; steps = EVAL_STEPS. Returns the
     reconstruction in x's shape: `out` if given (any such strides, written in place), a new NCHW tensor otherwise."""
-    _check('nmf2d', x=x, bases=bases, out=out)
+    check('nmf2d', x=x, bases=bases, out=out)
     _no_grad('nmf2d', x, bases)
     xs = group_view('nmf2d', x, spatial, S)
     G, D, N = x.shape[0] * int(S), xs[0][1].shape[1], xs[0][1].shape[2]

@@ -20,7 +20,7 @@ call. hipnet.nmf stays the inference module and keeps refusing gradients.
 import torch
 
 from hipnet import nmf as N
-from hipnet.nmf import _check
+from hipnet.nhwc import check
 
 
 def _nchw(t, c0, ch):
@@ -72,7 +72,7 @@ def hams_train(low, specs, bases, steps):
     cat. With a gradient required the backward is the one-step gradient above."""
     specs = [(bool(sp), int(c0), int(ch), int(S)) for sp, c0, ch, S in specs]
     bases = list(bases)
-    _check('hams_train', low=low, **{'bases{}'.format(i): b for i, b in enumerate(bases)})
+    check('hams_train', low=low, **{'bases{}'.format(i): b for i, b in enumerate(bases)})
     if low.ndim != 4 or low.numel() == 0:
         raise ValueError('hams_train: low {}: expected NHWC (B, h, w, Cp), nothing empty'.format(tuple(low.shape)))
     B, h, w, cp = low.shape

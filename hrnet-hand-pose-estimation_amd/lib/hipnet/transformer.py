@@ -15,29 +15,12 @@ qkv alone and its backward recomputes the softmax.
 import torch
 
 from hipnet import _capi as C
+from hipnet.nhwc import check, contiguous, wants_grad
 
 OP_LAYERNORM, OP_LINEAR, OP_ATTENTION, OP_FRAME_MEAN = (
     C.VALUES['HR_TF_' + n] for n in ('LAYERNORM', 'LINEAR', 'ATTENTION', 'FRAME_MEAN'))
 ACT_NONE, ACT_GELU = C.VALUES['HR_TF_ACT_NONE'], C.VALUES['HR_TF_ACT_GELU']
 _ACTS = {None: ACT_NONE, 'none': ACT_NONE, 'gelu': ACT_GELU}
-
-
-def _check(name, **tensors):
-    for k, t in tensors.items():
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError('{}: {} must be a HIP-device tensor (there is no CPU path in this build)'.format(name, k))
-        if t.dtype != torch.float32:
-            raise ValueError('{}: {} is {}: float32 only'.format(name, k, t.dtype))
-
-
-def _c(t):
-    return None if t is None else t.contiguous()
-
-
-def _wants_grad(*ts):
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
 def supported(op, a, b=0):
@@ -84,15 +67,15 @@ class _LayerNormFn(torch.autograd.Function):
 
 def layer_norm(x, weight, bias, eps=1e-5):
     """LayerNorm over the last axis of x (..., C); weight, bias (C,)"""
-    _check('layer_norm', x=x, weight=weight, bias=bias)
+    check('layer_norm', x=x, weight=weight, bias=bias)
     Cc = x.shape[-1] if x.ndim else 0
     if x.ndim < 1 or x.numel() == 0 or tuple(weight.shape) != (Cc,) or tuple(bias.shape) != (Cc,):
         raise ValueError('layer_norm: x {}, weight {}, bias {}: expected (..., C), (C,), (C,), nothing empty'.format(
             tuple(x.shape), tuple(weight.shape), tuple(bias.shape)))
     if not supported(OP_LAYERNORM, Cc):
         raise ValueError('layer_norm: C = {}: no kernel for this width'.format(Cc))
-    x, weight, bias = _c(x), _c(weight), _c(bias)
-    if _wants_grad(x, weight, bias):
+    x, weight, bias = contiguous(x), contiguous(weight), contiguous(bias)
+    if wants_grad(x, weight, bias):
         return _LayerNormFn.apply(x, weight, bias, float(eps))
     return _ln_forward(x.detach(), weight.detach(), bias.detach(), float(eps))
 
@@ -139,7 +122,7 @@ def linear(x, weight, bias=None, act=None, residual=None, row_scale=None):
     """y = [residual +] row_scale[row] * act(x weight^T + bias): x (..., Cin), weight (Cout, Cin), bias (Cout,) or None,
     act None or 'gelu' (exact), residual y's shape, row_scale one value per row (no gradient: it carries the
     stochastic-depth keep flags)"""
-    _check('linear', x=x, weight=weight, bias=bias, residual=residual, row_scale=row_scale)
+    check('linear', x=x, weight=weight, bias=bias, residual=residual, row_scale=row_scale)
     if act not in _ACTS:
         raise ValueError('linear: act {!r}: None or \'gelu\''.format(act))
     if x.ndim < 1 or weight.ndim != 2 or x.numel() == 0 or weight.numel() == 0 or x.shape[-1] != weight.shape[1]:
@@ -155,10 +138,10 @@ def linear(x, weight, bias=None, act=None, residual=None, row_scale=None):
         raise ValueError('linear: residual {}: expected {}'.format(tuple(residual.shape), tuple(x.shape[:-1]) + (Cout,)))
     if row_scale is not None and row_scale.numel() != rows:
         raise ValueError('linear: row_scale has {} values for {} rows'.format(row_scale.numel(), rows))
-    x, weight, bias, residual = _c(x), _c(weight), _c(bias), _c(residual)
+    x, weight, bias, residual = contiguous(x), contiguous(weight), contiguous(bias), contiguous(residual)
     rs = None if row_scale is None else row_scale.detach().contiguous()
     a = _ACTS[act]
-    if _wants_grad(x, weight, bias, residual):
+    if wants_grad(x, weight, bias, residual):
         return _LinearFn.apply(x, weight, bias, residual, rs, a)
     det = lambda t: None if t is None else t.detach()
     return _linear_forward(x.detach(), weight.detach(), det(bias), det(residual), rs, a, False)[0]
@@ -198,7 +181,7 @@ class _AttentionFn(torch.autograd.Function):
 def attention(qkv, heads, scale):
     """qkv (S, N, 3 * C) or (S, N, 3, heads, hd), packed [q | k | v] as nn.Linear(C, 3 C) leaves it -> (S, N, C):
     softmax(q k^T * scale) v per (sequence, head)"""
-    _check('attention', qkv=qkv)
+    check('attention', qkv=qkv)
     heads = int(heads)
     if qkv.ndim == 5:
         qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], -1)
@@ -209,8 +192,8 @@ def attention(qkv, heads, scale):
     if not supported(OP_ATTENTION, N, hd):
         raise ValueError('attention: N = {} tokens, hd = {}: no kernel for this shape (1 <= N <= 64, hd <= 128)'.format(
             N, hd))
-    qkv = _c(qkv)
-    if _wants_grad(qkv):
+    qkv = contiguous(qkv)
+    if wants_grad(qkv):
         return _AttentionFn.apply(qkv, heads, hd, float(scale))
     return _attn_forward(qkv.detach(), heads, hd, float(scale))
 
@@ -253,14 +236,14 @@ class _FrameMeanFn(torch.autograd.Function):
 def frame_mean(x, weight, bias=None):
     """out[s] = sum_f weight[f] * x[s, f] + bias: x (S, F, ...), weight F values (a Conv1d(F, 1, 1) weight (1, F, 1) is
     taken as it is), bias one value or None -> (S, ...)"""
-    _check('frame_mean', x=x, weight=weight, bias=bias)
+    check('frame_mean', x=x, weight=weight, bias=bias)
     if x.ndim < 3 or x.numel() == 0 or weight.numel() != x.shape[1] or (bias is not None and bias.numel() != 1):
         raise ValueError('frame_mean: x {}, weight {}: expected (S, F, ...), F weights and one bias'.format(
             tuple(x.shape), tuple(weight.shape)))
     if not supported(OP_FRAME_MEAN, x.shape[1]):
         raise ValueError('frame_mean: F = {}: no kernel for this many frames'.format(x.shape[1]))
-    x, weight, bias = _c(x), _c(weight), _c(bias)
-    if _wants_grad(x, weight, bias):
+    x, weight, bias = contiguous(x), contiguous(weight), contiguous(bias)
+    if wants_grad(x, weight, bias):
         return _FrameMeanFn.apply(x, weight.reshape(-1), None if bias is None else bias.reshape(1))
     return _fmean_forward(x.detach(), weight.detach(), None if bias is None else bias.detach())
 
@@ -294,12 +277,12 @@ def _add_rows_forward(x, pos):
 def add_rows(x, pos):
     """y[r] = x[r] + pos[r % period]: x (rows, C), pos (period, C), period divides rows (a position embedding added to
     every sequence)"""
-    _check('add_rows', x=x, pos=pos)
+    check('add_rows', x=x, pos=pos)
     if x.ndim != 2 or pos.ndim != 2 or x.numel() == 0 or pos.numel() == 0 or x.shape[1] != pos.shape[1] \
             or x.shape[0] % pos.shape[0]:
         raise ValueError('add_rows: x {}, pos {}: expected (rows, C) and (period, C), period dividing rows'.format(
             tuple(x.shape), tuple(pos.shape)))
-    x, pos = _c(x), _c(pos)
-    if _wants_grad(x, pos):
+    x, pos = contiguous(x), contiguous(pos)
+    if wants_grad(x, pos):
         return _AddRowsFn.apply(x, pos)
     return _add_rows_forward(x.detach(), pos.detach())

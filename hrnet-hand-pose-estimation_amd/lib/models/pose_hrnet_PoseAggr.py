@@ -36,6 +36,7 @@ import torch.nn as nn
 from deformable_conv import DeformConv
 from hipnet import _capi as C
 from hipnet import eager as E
+from hipnet import nhwc
 from models.pose_hrnet import BN_MOMENTUM, BasicBlock, Bottleneck, HighResolutionModule, _Unit, blocks_dict  # noqa: F401
 from models.pose_hrnet_softmax import PoseHighResolutionNet as _SoftmaxNet
 from models.pose_hrnet_softmax import _SpatialSoftmax
@@ -172,12 +173,12 @@ class PoseHighResolutionNet(_SoftmaxNet):
         diff = torch.empty_like(x)
         for g in range(5):
             _lincomb(diff[g * B:(g + 1) * B], [xs[2], xs[g]], [1.0, -1.0])
-        cur = E.ToNHWC.apply(diff, net.convs['offset_feats.0.conv1'].Cin_pad, tdt)
+        cur = nhwc.ToNHWC.apply(diff, net.convs['offset_feats.0.conv1'].Cin_pad, tdt)
         for unit in self.offset_feats:
             cur = E.basic_block(cur, unit)
         warped = []
         for k, d in enumerate(self.dilation_rates, 1):
-            off = E.ToNCHW.apply(E.DilatedConv.apply(cur, getattr(self, 'offsets{}'.format(k)).weight, d), nj * 18)
+            off = nhwc.ToNCHW.apply(E.DilatedConv.apply(cur, getattr(self, 'offsets{}'.format(k)).weight, d), nj * 18)
             warped.append(getattr(self, 'deform_conv{}'.format(k))(x, off))
         w = E.LinComb.apply([0.2] * len(warped), *warped)
         return E.LinComb.apply(list(FRAME_WEIGHTS), *[w[g * B:(g + 1) * B] for g in range(5)])

@@ -76,12 +76,10 @@ import os
 import torch
 import torch.nn as nn
 
-from hipnet import _capi as C
 from hipnet import burger_train as BT
+from hipnet import nhwc
 from hipnet import nmf as N
 from hipnet import nmf_train as NT
-from hipnet import swin as S
-from hipnet import swin_train as ST
 
 logger = logging.getLogger(__name__)
 
@@ -199,56 +197,6 @@ def check_config(config):
                                                                                          config.DATASET.NUM_JOINTS))
 
 
-def conv_nhwc(x, packed, cout, ks, bias=None, in_affine=None, in_relu=False, into=None):
-    """f32 NHWC stride-1 convolution on hrnet_conv2d: x (B, H, W, Cin), packed [cout][ks * ks][Cin]; in_affine: the
-    producer's folded BatchNorm (scale, shift), applied with in_relu when x is loaded; `into`: accumulate into this
-    (B, H, W, cout) tensor instead of writing a new one"""
-    B, H, W, cin = x.shape
-    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device) if into is None else into
-    scale, shift = (None, None) if in_affine is None else in_affine
-    with torch.cuda.device(x.device):
-        C.call('hrnet_conv2d', C.HR_F32, x.data_ptr(), packed.data_ptr(), C.ptr(scale), C.ptr(shift), C.ptr(bias),
-               y.data_ptr(), None, B, H, W, cin, H, W, cout, ks, 1, 0, 1 if in_relu else 0, 0 if into is None else 1,
-               C.stream_ptr())
-    return y
-
-
-def conv3x3_taps(x, taps, cout):
-    """the same 3x3 convolution as nine 1x1 launches over displaced windows that accumulate into y
-    (hrnet_conv2d_dilated3x3 with dilation 1): nine sums of Cin terms in place of one of 9 Cin. x (B, H, W, Cin) as it is (no
-    prologue), taps [9][cout][Cin] of _pack_taps; no bias"""
-    B, H, W, cin = x.shape
-    y = torch.empty((B, H, W, cout), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        C.call('hrnet_conv2d_dilated3x3', C.HR_F32, x.data_ptr(), taps.data_ptr(), 4 * cout * cin, y.data_ptr(), B, H, W, cin,
-               cout, 1, C.stream_ptr())
-    return y
-
-
-def _pack_taps(weight, cin_pad, cout_pad):
-    """OIHW 3x3 weight -> nine packed 1x1 matrices [9][cout_pad][cin_pad], tap t = 3 r + s"""
-    return torch.cat([_pack(weight[:, :, t // 3:t // 3 + 1, t % 3:t % 3 + 1], cin_pad, cout_pad) for t in range(9)])
-
-
-def _pack(weight, cin_pad, cout_pad, scale=None):
-    """OIHW weight, optionally scaled per output channel, -> [cout_pad][ks * ks][cin_pad] on the device"""
-    w = weight.detach().float()
-    if scale is not None:
-        w = (w.double() * scale.double().reshape(-1, 1, 1, 1)).float()
-    w = w.contiguous()
-    co, ci, ks, _ = w.shape
-    out = torch.empty(cout_pad * ks * ks * cin_pad, dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        C.call('hrnet_pack_weights', C.HR_F32, w.data_ptr(), out.data_ptr(), co, ci, ks, cout_pad, cin_pad, 0, C.stream_ptr())
-    return out
-
-
-def _padded(v, n):
-    out = torch.zeros(n, dtype=torch.float32, device=v.device)
-    out[:v.numel()] = v.detach().float().reshape(-1)
-    return out
-
-
 def _fold(bn):
     """eval-mode BatchNorm as (scale, shift), float64"""
     scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
@@ -302,20 +250,24 @@ class HamNet(nn.Module):
         if self._plan is not None and key == self._plan_key:
             return self._plan
         h = self.hamburger
-        cin, e = S.pad16(self.in_channel), S.pad16(self.embed_dim)
-        cp, mp, ap, jp = S.pad16(h.channels), S.pad16(h.mid), S.pad16(ALIGN_CHANNELS), S.pad16(self.num_joints)
-        affine = lambda bn, n: tuple(_padded(v, n) for v in _fold(bn))
+        pad16, padded, pack = nhwc.pad16, nhwc.padded, nhwc.conv_pack
+        cin, e = pad16(self.in_channel), pad16(self.embed_dim)
+        cp, mp, ap, jp = pad16(h.channels), pad16(h.mid), pad16(ALIGN_CHANNELS), pad16(self.num_joints)
+        affine = lambda bn, n: tuple(padded(v, n) for v in _fold(bn))
+        # a 3x3 as the nine [cout_pad][cin_pad] matrices of its taps, tap t = 3 r + s
+        taps = lambda conv, ip, op: nhwc.pack_taps(conv.weight.detach().float().contiguous(), conv.out_channels,
+                                                   conv.in_channels, op, ip, 0)
         # the cheese as the (C, mid) matrix of a plain NMF-engine product, zero columns up to the padded width
         w_cheese = torch.zeros((h.channels, mp), dtype=torch.float32, device=h.cheese.conv.weight.device)
         w_cheese[:, :h.mid] = h.cheese.conv.weight.detach().float().reshape(h.mid, h.channels).t()
         self._plan = dict(
             cin=cin, e=e, cp=cp, mp=mp, ap=ap, jp=jp,
-            w_squeeze=_pack_taps(self.squeeze.conv.weight, cin, e), bn_squeeze=affine(self.squeeze.bn, e),
-            w_lower=_pack(h.lower_bread[0].weight, e, cp), b_lower=_padded(h.lower_bread[0].bias, cp),
+            w_squeeze=taps(self.squeeze.conv, cin, e), bn_squeeze=affine(self.squeeze.bn, e),
+            w_lower=pack(h.lower_bread[0].weight, e, cp), b_lower=padded(h.lower_bread[0].bias, cp),
             w_cheese=w_cheese, bn_cheese=affine(h.cheese.bn, mp),
-            w_upper=_pack(h.upper_bread.weight, mp, e, h.coef_ham.detach().double().expand(self.embed_dim)),
-            w_align=_pack_taps(self.align.conv.weight, e, ap), bn_align=affine(self.align.bn, ap),
-            w_fc=_pack(self.fc[1].weight, ap, jp), b_fc=_padded(self.fc[1].bias, jp))
+            w_upper=pack(h.upper_bread.weight, mp, e, h.coef_ham.detach().double().expand(self.embed_dim)),
+            w_align=taps(self.align.conv, e, ap), bn_align=affine(self.align.bn, ap),
+            w_fc=pack(self.fc[1].weight, ap, jp), b_fc=padded(self.fc[1].bias, jp))
         self._plan_key = key
         return self._plan
 
@@ -372,22 +324,22 @@ class HamNet(nn.Module):
             raise ValueError('drop_keep {}: expected ({}, {})'.format(tuple(getattr(drop_keep, 'shape', ())), B,
                                                                       ALIGN_CHANNELS))
         h = self.hamburger
-        keep = torch.zeros((B, S.pad16(ALIGN_CHANNELS)), dtype=torch.float32, device=dev)
+        keep = torch.zeros((B, nhwc.pad16(ALIGN_CHANNELS)), dtype=torch.float32, device=dev)
         keep[:, :ALIGN_CHANNELS] = drop_keep.to(device=dev, dtype=torch.float32)
         with torch.no_grad():
             nb = [N.normalise_bases(b.to(device=dev, dtype=torch.float32)) for b in bases]
         specs = [(ham.spatial, c0, ch, ham.S) for ham, c0, ch in h.hams()]
-        x = BT.to_nhwc(features.float(), S.pad16(self.in_channel))
+        x = nhwc.to_nhwc(features.float(), nhwc.pad16(self.in_channel))
         sq = BT.conv_bn_relu_train(x, self.squeeze.conv, self.squeeze.bn, 3)
-        low = BT.conv1x1_train(sq, h.lower_bread[0], relu_out=True)
+        low = nhwc.conv1x1_train(sq, h.lower_bread[0], relu_out=True)
         y = NT.hams_train(low, specs, nb, self.train_steps)
         y = BT.conv_bn_relu_train(y, h.cheese.conv, h.cheese.bn, 1)
-        y = BT.conv1x1_train(y, h.upper_bread)
+        y = nhwc.conv1x1_train(y, h.upper_bread)
         y = BT.burger_mix(y, sq, h.coef_ham, h.coef_shortcut)
         y = BT.conv_bn_relu_train(y, self.align.conv, self.align.bn, 3)
-        y = BT.conv1x1_train(BT.dropout2d(y, keep), self.fc[1])
+        y = nhwc.conv1x1_train(BT.dropout2d(y, keep), self.fc[1])
         self._plan = None                 # the running statistics were written through their pointers, not their version
-        return _SpatialSoftmax.apply(ST.to_nchw(y, self.num_joints), self.trainable_temp)
+        return _SpatialSoftmax.apply(nhwc.to_nchw(y, self.num_joints), self.trainable_temp)
 
     def head_forward(self, features, bases=None, drop_keep=None):
         """features (B, 480, h, w) NCHW on the device -> heat maps: everything after the backbone. bases: None (drawn here
@@ -411,13 +363,10 @@ class HamNet(nn.Module):
         with torch.no_grad():
             p = self._head_plan()
             dev = features.device
-            x = torch.empty((B, hh, ww, p['cin']), dtype=torch.float32, device=dev)
-            f = features.detach().float().contiguous()
-            with torch.cuda.device(dev):
-                C.call('hrnet_nchw_to_nhwc', C.HR_F32, f.data_ptr(), x.data_ptr(), B, hh, ww, p['cin'], self.in_channel,
-                       C.stream_ptr())
-            z = conv3x3_taps(x, p['w_squeeze'], p['e'])                               # squeeze before its BatchNorm
-            low = conv_nhwc(z, p['w_lower'], p['cp'], 1, bias=p['b_lower'], in_affine=p['bn_squeeze'], in_relu=True).relu_()
+            x = nhwc.to_nhwc(features.detach().float(), p['cin'])
+            z = nhwc.conv3x3_taps(x, p['w_squeeze'], p['e'])                          # squeeze before its BatchNorm
+            low = nhwc.conv_nhwc(z, p['w_lower'], p['cp'], 1, bias=p['b_lower'], in_affine=p['bn_squeeze'],
+                                 in_relu=True).relu_()
             h = self.hamburger
             cheese_in = torch.empty_like(low)             # the hams write every real channel; no other is read
             for (ham, c0, ch), b in zip(h.hams(), bases):
@@ -431,10 +380,10 @@ class HamNet(nn.Module):
             scale, shift = p['bn_squeeze']
             block = torch.addcmul(shift, z, scale).relu_().mul_(h.coef_shortcut.detach())
             # + coef_ham * upper_bread(relu(bn(mid))); the block's own ReLU, then align before its BatchNorm
-            conv_nhwc(mid, p['w_upper'], p['e'], 1, in_affine=p['bn_cheese'], in_relu=True, into=block)
-            y = conv3x3_taps(block.relu_(), p['w_align'], p['ap'])
-            y = conv_nhwc(y, p['w_fc'], p['jp'], 1, bias=p['b_fc'], in_affine=p['bn_align'], in_relu=True)
-            return S.heatmap_softmax(y, self.num_joints, self.trainable_temp)
+            nhwc.conv_nhwc(mid, p['w_upper'], p['e'], 1, in_affine=p['bn_cheese'], in_relu=True, into=block)
+            y = nhwc.conv3x3_taps(block.relu_(), p['w_align'], p['ap'])
+            y = nhwc.conv_nhwc(y, p['w_fc'], p['jp'], 1, bias=p['b_fc'], in_affine=p['bn_align'], in_relu=True)
+            return nhwc.heatmap_softmax(y, self.num_joints, self.trainable_temp)
 
     def forward(self, x, bases=None, drop_keep=None):
         self._refuse(x)

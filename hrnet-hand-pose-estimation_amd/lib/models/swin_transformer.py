@@ -16,8 +16,9 @@ forward(x): x (B, 3, H, W)
   6. softmax(maps * trainable_temp) over the positions of each map                                                :824-827
 returns (heatmap_pred (B, J, Hm, Wm), trainable_temp).
 
-Every arithmetic step is a launch through the C ABI: hipnet.transformer (LayerNorm, linear with GELU / residual) and
-hipnet.swin (window attention in token order, the two gathers, the decoder on the f32 NHWC convolution entry). A block is
+Every arithmetic step is a launch through the C ABI: hipnet.transformer (LayerNorm, linear with GELU / residual),
+hipnet.swin (window attention in token order, the two gathers) and hipnet.nhwc (the decoder on the f32 NHWC convolution
+entry). A block is
 7 launches: LayerNorm, qkv, attention, proj + residual, LayerNorm, fc1 + GELU, fc2 + residual. The attention kernel finds
 a window's tokens arithmetically: there is no partition, roll, pad or reverse pass, and the qkv linear runs on the unpadded
 tokens only (a padded token's q, k, v are the qkv bias). The Swin output (B, H W, C) is the decoder's NHWC input as it is.
@@ -55,6 +56,7 @@ import os
 import torch
 import torch.nn as nn
 
+from hipnet import nhwc
 from hipnet import swin as S
 from hipnet import swin_train as ST
 from hipnet import transformer as T
@@ -356,25 +358,21 @@ class SwinPose(nn.Module):
         key = tuple((t.data_ptr(), t._version) for t in tensors)
         if self._plan is not None and key == self._plan_key:
             return self._plan
-
-        def padded(v, n):
-            out = torch.zeros(n, dtype=torch.float32, device=v.device)
-            out[:v.numel()] = v.detach().float()
-            return out
-
         mods = list(self.decoder)
         steps, cin_pad = [], mods[0].in_channels
         for i in range(0, len(mods) - 1, 4):
             up, conv, bn = mods[i], mods[i + 1], mods[i + 2]
-            cop = S.pad16(up.out_channels)
+            cop = nhwc.pad16(up.out_channels)
             scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
             shift = (conv.bias.detach().double() - bn.running_mean.detach().double()) * scale + bn.bias.detach().double()
-            steps.append(dict(cout=cop, w_up=S.conv_transpose_pack(up.weight, cin_pad, cop), b_up=padded(up.bias, cop),
-                              w_pw=S.conv_pack(conv.weight, cop, cop), scale=padded(scale, cop), shift=padded(shift, cop)))
+            steps.append(dict(cout=cop, w_up=nhwc.conv_transpose_pack(up.weight, cin_pad, cop),
+                              b_up=nhwc.padded(up.bias, cop), w_pw=nhwc.conv_pack(conv.weight, cop, cop),
+                              affine=(nhwc.padded(scale, cop), nhwc.padded(shift, cop))))
             cin_pad = cop
         final = mods[-1]
-        jp = S.pad16(final.out_channels)
-        self._plan = dict(steps=steps, jp=jp, w_final=S.conv_pack(final.weight, cin_pad, jp), b_final=padded(final.bias, jp))
+        jp = nhwc.pad16(final.out_channels)
+        self._plan = dict(steps=steps, jp=jp, w_final=nhwc.conv_pack(final.weight, cin_pad, jp),
+                          b_final=nhwc.padded(final.bias, jp))
         self._plan_key = key
         return self._plan
 
@@ -382,15 +380,14 @@ class SwinPose(nn.Module):
         """x (B, H * W, C), the Swin output, read as NHWC -> heat maps (B, J, H 2^steps, W 2^steps)"""
         plan = self._decoder_plan()
         y = x.reshape(x.shape[0], H, W, x.shape[2])
-        scale = shift = None
+        affine = None                 # the step before's folded BatchNorm, applied with its ReLU when the next one loads
         for st in plan['steps']:
-            y = S.conv_nhwc(y, st['w_up'], st['cout'], 3, up=True, bias=st['b_up'], in_scale=scale, in_shift=shift,
-                            in_relu=scale is not None)
-            y = S.conv_nhwc(y, st['w_pw'], st['cout'], 1)
-            scale, shift = st['scale'], st['shift']
-        y = S.conv_nhwc(y, plan['w_final'], plan['jp'], 1, bias=plan['b_final'], in_scale=scale, in_shift=shift,
-                        in_relu=True)
-        return S.heatmap_softmax(y, self.num_joints, self.trainable_temp)
+            y = nhwc.conv_nhwc(y, st['w_up'], st['cout'], 3, up=True, bias=st['b_up'], in_affine=affine,
+                               in_relu=affine is not None)
+            y = nhwc.conv_nhwc(y, st['w_pw'], st['cout'], 1)
+            affine = st['affine']
+        y = nhwc.conv_nhwc(y, plan['w_final'], plan['jp'], 1, bias=plan['b_final'], in_affine=affine, in_relu=True)
+        return nhwc.heatmap_softmax(y, self.num_joints, self.trainable_temp)
 
     # ---- the model -----------------------------------------------------------------------------------------------
     def _refuse(self, x):
@@ -419,7 +416,7 @@ class SwinPose(nn.Module):
         for i in range(0, len(mods) - 1, 4):
             y = ST.decoder_step(y, mods[i], mods[i + 1], mods[i + 2])
         self._plan = None                 # the running statistics were written through their pointers, not their version
-        y = ST.to_nchw(ST.decoder_final(y, mods[-1]), self.num_joints)
+        y = nhwc.to_nchw(nhwc.conv1x1_train(y, mods[-1]), self.num_joints)
         return _SpatialSoftmax.apply(y, self.trainable_temp)
 
     def _check_flags(self, drop_flags, B):

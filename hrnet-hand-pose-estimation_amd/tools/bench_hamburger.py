@@ -344,8 +344,8 @@ def stage_times(model, features, bases, keep, repeats, warmup):
     import torch
     import torch.nn.functional as Fn
     from hipnet import burger_train as BT
+    from hipnet import nhwc
     from hipnet import nmf_train as NT
-    from hipnet import swin_train as ST
     from models.pose_hrnet_softmax import _SpatialSoftmax
     h = model.hamburger
     steps, J = model.train_steps, model.num_joints
@@ -369,18 +369,18 @@ def stage_times(model, features, bases, keep, repeats, warmup):
     stages = {
         'squeeze': (features, False, lambda x: BT.conv_bn_relu_train(x, model.squeeze.conv, model.squeeze.bn, 3),
                     lambda x: _torch_cbr_train(model.squeeze, x)),
-        'lower_bread': (z, True, lambda x: BT.conv1x1_train(x, h.lower_bread[0], True),
+        'lower_bread': (z, True, lambda x: nhwc.conv1x1_train(x, h.lower_bread[0], True),
                         lambda x: torch.relu(Fn.conv2d(x, h.lower_bread[0].weight, h.lower_bread[0].bias))),
         'hams': (low, True, lambda x: NT.hams_train(x, specs, nb, steps), t_hams),
         'cheese': (ham, True, lambda x: BT.conv_bn_relu_train(x, h.cheese.conv, h.cheese.bn, 1),
                    lambda x: _torch_cbr_train(h.cheese, x)),
-        'upper_bread': (mid, True, lambda x: BT.conv1x1_train(x, h.upper_bread), lambda x: Fn.conv2d(x, h.upper_bread.weight)),
+        'upper_bread': (mid, True, lambda x: nhwc.conv1x1_train(x, h.upper_bread), lambda x: Fn.conv2d(x, h.upper_bread.weight)),
         'mix': (up, True, lambda x: BT.burger_mix(x, s_nhwc, h.coef_ham, h.coef_shortcut),
                 lambda x: torch.relu(h.coef_ham * x + h.coef_shortcut * s_nchw)),
         'align': (blk, True, lambda x: BT.conv_bn_relu_train(x, model.align.conv, model.align.bn, 3),
                   lambda x: _torch_cbr_train(model.align, x)),
         'dropout': (al, True, lambda x: BT.dropout2d(x, keep), lambda x: x * kview),
-        'fc': (al, True, lambda x: _SpatialSoftmax.apply(ST.to_nchw(BT.conv1x1_train(x, model.fc[1]), J),
+        'fc': (al, True, lambda x: _SpatialSoftmax.apply(nhwc.to_nchw(nhwc.conv1x1_train(x, model.fc[1]), J),
                                                          model.trainable_temp), t_fc),
     }
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

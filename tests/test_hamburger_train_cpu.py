@@ -184,6 +184,7 @@ def test_abi_names_are_declared_exported_and_refuse_by_argument_check():
 
 def test_refusals_without_a_device(monkeypatch):
     from hipnet import burger_train as BT
+    from hipnet import nhwc
     from hipnet import nmf_train as NT
     from models import pose_hrnet_hamburger as M
     plain = M.get_pose_net(_cfg(SMALL), is_train=False)
@@ -213,8 +214,8 @@ def test_refusals_without_a_device(monkeypatch):
     x, c = torch.zeros(2, 5, 7, 48), torch.ones(1)
     conv, bn = torch.nn.Conv2d(48, 16, 1, bias=False), torch.nn.BatchNorm2d(16)
     for call in (lambda: BT.burger_mix(x, x, c, c), lambda: BT.dropout2d(x, torch.ones(2, 48)),
-                 lambda: BT.conv_bn_relu_train(x, conv, bn, 1), lambda: BT.conv1x1_train(x, conv),
-                 lambda: BT.to_nhwc(torch.zeros(2, 3, 5, 7), 16),
+                 lambda: BT.conv_bn_relu_train(x, conv, bn, 1), lambda: nhwc.conv1x1_train(x, conv),
+                 lambda: nhwc.to_nhwc(torch.zeros(2, 3, 5, 7), 16),
                  lambda: NT.hams_train(x, [(True, 0, 48, 1)], [torch.zeros(2, 48, 8)], 6)):
         with pytest.raises(ValueError, match='HIP-device'):
             call()

@@ -138,6 +138,7 @@ def test_backbone_checkpoint_is_loaded_non_strictly(tmp_path):
 
 
 def test_refusals():
+    from hipnet import nhwc
     from hipnet import swin as S
     from models import swin_transformer as M
     for opts, match in ((['MODEL.FF_TYPE', 'conv'], 'FF_TYPE'),
@@ -164,9 +165,9 @@ def test_refusals():
     c = torch.zeros(1, 4, 24)
     for call in (lambda: S.window_attention(c, c[0, 0], torch.zeros(169, 2), 2, 2, 2, 7, 0, 1.0),
                  lambda: S.merge_ln(c, 2, 2), lambda: S.patch_rows(torch.zeros(1, 3, 8, 8), 2),
-                 lambda: S.conv_transpose_pack(torch.zeros(8, 16, 3, 3)), lambda: S.conv_pack(torch.zeros(16, 8, 1, 1)),
-                 lambda: S.conv_nhwc(torch.zeros(1, 2, 2, 8), torch.zeros(128), 16, 1),
-                 lambda: S.heatmap_softmax(torch.zeros(1, 2, 2, 32), 21, torch.ones(()))):
+                 lambda: nhwc.conv_transpose_pack(torch.zeros(8, 16, 3, 3)), lambda: nhwc.conv_pack(torch.zeros(16, 8, 1, 1)),
+                 lambda: nhwc.conv_nhwc(torch.zeros(1, 2, 2, 8), torch.zeros(128), 16, 1),
+                 lambda: nhwc.heatmap_softmax(torch.zeros(1, 2, 2, 32), 21, torch.ones(()))):
         with pytest.raises(ValueError, match='HIP-device'):
             call()
 

@@ -148,7 +148,7 @@ def test_decoder_step_against_conv_transpose2d(size, cin):
     convolution, and the folded (scale, shift) + ReLU is applied by the next launch's load (an identity 1x1 here).
     MI355X, err / e_ref / bound: 1x1 96 -> 48 1.2e-07 / 1.7e-07 / 8.0e-07, 4x4 96 -> 48 2.7e-07 / 2.7e-07 / 1.2e-06,
     1x1 768 -> 384 9.0e-07 / 4.9e-07 / 2.1e-06, 4x4 768 -> 384 9.9e-07 / 6.9e-07 / 2.9e-06."""
-    from hipnet import swin as S
+    from hipnet import nhwc
     g = torch.Generator().manual_seed(size * 1000 + cin)
     B, cout = 2, cin // 2
     f = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32).double()
@@ -169,10 +169,11 @@ def test_decoder_step_against_conv_transpose2d(size, cin):
     d = lambda t: t.float().cuda()
     scale = gamma / torch.sqrt(var + 1e-5)
     shift = (b1 - mean) * scale + beta
-    y = S.conv_nhwc(d(x).permute(0, 2, 3, 1).contiguous(), S.conv_transpose_pack(d(wT)), cout, 3, up=True, bias=d(bT))
-    y = S.conv_nhwc(y, S.conv_pack(d(w1)), cout, 1)
+    y = nhwc.conv_nhwc(d(x).permute(0, 2, 3, 1).contiguous(), nhwc.conv_transpose_pack(d(wT)), cout, 3, up=True,
+                       bias=d(bT))
+    y = nhwc.conv_nhwc(y, nhwc.conv_pack(d(w1)), cout, 1)
     eye = torch.eye(cout, dtype=torch.float32, device='cuda').reshape(cout, cout, 1, 1)
-    y = S.conv_nhwc(y, S.conv_pack(eye), cout, 1, in_scale=d(scale), in_shift=d(shift), in_relu=True)
+    y = nhwc.conv_nhwc(y, nhwc.conv_pack(eye), cout, 1, in_affine=(d(scale), d(shift)), in_relu=True)
     torch.cuda.synchronize()
     assert tuple(y.shape) == (B, 2 * size, 2 * size, cout)
     bad = []

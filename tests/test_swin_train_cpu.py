@@ -86,18 +86,35 @@ def test_new_entries_refuse_by_argument_check():
 
 
 def test_swin_train_ops_refuse_before_any_device_call():
+    from hipnet import nhwc
     from hipnet import swin_train as ST
     c = torch.zeros(1, 4, 24)
     up, conv, bn = torch.nn.ConvTranspose2d(16, 16, 3, 2, 1, 1), torch.nn.Conv2d(16, 16, 1), torch.nn.BatchNorm2d(16)
     for call in (lambda: ST.window_attention(c, c[0, 0], torch.zeros(169, 2), 2, 2, 2, 7, 0, 1.0),
                  lambda: ST.merge_gather(c, 2, 2), lambda: ST.patch_rows(torch.zeros(1, 3, 8, 8), 2),
                  lambda: ST.decoder_step(torch.zeros(1, 2, 2, 16), up, conv, bn),
-                 lambda: ST.decoder_final(torch.zeros(1, 2, 2, 16), conv), lambda: ST.to_nchw(torch.zeros(1, 2, 2, 32), 21)):
+                 lambda: nhwc.conv1x1_train(torch.zeros(1, 2, 2, 16), conv),
+                 lambda: nhwc.to_nchw(torch.zeros(1, 2, 2, 32), 21)):
         with pytest.raises(ValueError, match='HIP-device'):
             call()
     # hipnet.swin keeps refusing gradients
     from hipnet import swin as S
     assert 'backward is not built' in open(S.__file__).read()
+
+
+def test_no_module_imports_a_private_name_of_another():
+    """the shared helpers are public names of hipnet.nhwc; hipnet._capi and hipnet._header are modules, not helpers"""
+    import re
+    lib = os.path.join(PKG, 'lib')
+    found = []
+    for folder, _, files in os.walk(lib):
+        for f in files:
+            if f.endswith('.py'):
+                for n, line in enumerate(open(os.path.join(folder, f)), 1):
+                    if re.search(r'from hipnet\.\w+ import _', line) or \
+                            re.search(r'from hipnet import .*\b_(?!capi|header)', line):
+                        found.append('{}:{}: {}'.format(os.path.relpath(os.path.join(folder, f), lib), n, line.strip()))
+    assert not found, found
 
 
 @pytest.mark.parametrize('backbone', ['pose_hrnet_softmax', ''])
