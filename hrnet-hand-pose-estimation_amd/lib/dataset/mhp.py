@@ -39,6 +39,9 @@ projection of joint j truncated to int; `collate` paints a black disc of radius 
 within 50 px of the centre (np.linalg.norm(p - centre) <= 50) is invisible, like one outside the frame. cv2.circle's
 rasterisation is not available: the painted pixels are those with (x - cx)^2 + (y - cy)^2 <= 50^2 (unpinned).
 
+MHP_CPM_kpt: the evaluation path of the reference's MHP_CPMDataset (MHP_CPMDataset.py:137-239), the reader of
+MODEL.NAME CPM; its class below says what a sample holds. The loader resizes the whole frame (no crop, no warp).
+
 Every batch also carries `hm_inverse` (N, 2, 3) float64: heat-map pixel -> original-image pixel, the inverse of the
 sample's heat-map matrix with the flip folded in. tools/evaluate_2D.py maps predictions and ground truth back through
 it; the reference scales x by 640/64 and y by 480/64 there (evaluate_2D.py:240-245), which does not invert its own
@@ -361,7 +364,85 @@ def paint_disc(img, centre, radius=OCCLUSION_RADIUS):
     return out
 
 
-READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq, 'MHP_mv': MHP_mv}
+def gaussian_map(height, width, cx, cy, sigma):
+    """exp(-d^2 / (2 sigma^2)) around (cx, cy) on a height x width grid, clipped to <= 1, values < 0.0099 set to 0
+    (MHP_CPMDataset.py:81-84 with :199-200, :222-223), float64"""
+    yy, xx = np.mgrid[0:int(height), 0:int(width)]
+    g = np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / 2.0 / sigma / sigma)
+    g[g > 1] = 1
+    g[g < 0.0099] = 0
+    return g
+
+
+def cpm_center(pose2d, width, height):
+    """((cx, cy), exception) of MHP_CPMDataset.py:171-183: per axis the mean of the largest coordinate below the size
+    and the smallest above 0; the middle of the frame, with `exception`, where no joint qualifies on an axis"""
+    center, exception = [], False
+    for axis, size in ((0, width), (1, height)):
+        v = np.asarray(pose2d)[:, axis]
+        below, above = v[v < size], v[v > 0]
+        if below.size and above.size:
+            center.append((below.max() + above.min()) / 2)
+        else:
+            center.append(size / 2)
+            exception = True
+    return tuple(center), exception
+
+
+class MHP_CPM_kpt(MHP):
+    """the evaluation path of the reference's MHP_CPMDataset (MHP_CPMDataset.py:137-239), the reader of MODEL.NAME CPM:
+    the whole frame resized to MODEL.IMAGE_SIZE (no crop, so x and y scale differently: TestResized(256) behind that is
+    the identity), BGR, normalised as (v - 128) / 256; `pose2d` (21, 2) in pixels of the stride-8 maps, `visibility`
+    (21, 1), `heatmaps` (22, H/8, W/8) - channel 0 the background 1 - max, channel i + 1 the sigma = DATASET.SIGMA
+    Gaussian of joint i at int(coordinate) / 8 - and `centermaps` (1, H, W), the sigma = 3 Gaussian at the hand's centre.
+    `hm_inverse` maps a stride-8 map pixel back to the 640 x 480 frame. The reference's training transforms
+    (RandomResized, RandomRotate, RandomCrop, RandomHorizontalFlip) are not built: is_train=True is refused."""
+    name = 'MHP_CPM_kpt'
+    stride = 8
+    mean = (128.0 / 255.0,) * 3           # (u / 255 - mean) / std = (u - 128) / 256
+    std = (256.0 / 255.0,) * 3
+    resize = True                         # the loader resizes the frame (hrnet_resize_normalize_u8), it does not warp it
+
+    def __init__(self, cfg, subset, is_train=False, seed=0):
+        if is_train:
+            raise ValueError('MHP_CPM_kpt: the training transforms of the reference (RandomResized, RandomRotate, '
+                             'RandomCrop, RandomHorizontalFlip) are not built: evaluation only')
+        MHP.__init__(self, cfg, subset, is_train, seed)
+        self.width, self.height = (int(v) for v in cfg.MODEL.IMAGE_SIZE)
+        if self.width % self.stride or self.height % self.stride:
+            raise ValueError('MHP_CPM_kpt: MODEL.IMAGE_SIZE {}: multiples of {}'.format(list(cfg.MODEL.IMAGE_SIZE),
+                                                                                       self.stride))
+        self.sigma = cfg.DATASET.SIGMA
+        self.exception = False
+
+    def __getitem__(self, key):
+        idx = key[0] if isinstance(key, tuple) else key
+        path = self.images[idx]
+        subdir = os.path.basename(os.path.dirname(path))
+        frame, _, view = os.path.splitext(os.path.basename(path))[0].split('_')
+        world = read_joints(os.path.join(self.data_dir, 'MHP', 'annotations', subdir, frame + '_joints.txt'))
+        if (subdir, view) not in self._calib:
+            self._calib[(subdir, view)] = read_calibration(self.data_dir, subdir, view)
+        rvec, tvec = self._calib[(subdir, view)]
+        sx, sy = self.width / FRAME_W, self.height / FRAME_H
+        pose2d = project_points(world[list(IDX_MHP)], rvec, tvec, INTRINSIC, DISTORTION) * np.array((sx, sy))
+        vis = visibility(pose2d, self.width, self.height)
+        center, self.exception = cpm_center(pose2d, self.width, self.height)
+        hh, hw = self.height // self.stride, self.width // self.stride
+        heat = np.zeros((len(pose2d) + 1, hh, hw), dtype=np.float32)
+        for i, (x, y) in enumerate(pose2d):
+            heat[i + 1] = gaussian_map(hh, hw, int(x) / self.stride, int(y) / self.stride, self.sigma)
+        heat[0] = 1.0 - heat[1:].max(axis=0)
+        centermap = gaussian_map(self.height, self.width, center[0], center[1], 3).astype(np.float32)[None]
+        s = self.stride
+        return {'paths': [path], 'frames': 1, 'views': 1, 'inverse': np.array([[[1 / sx, 0., 0.], [0., 1 / sy, 0.]]]),
+                'hm_inverse': np.array([[[s / sx, 0., 0.], [0., s / sy, 0.]]]), 'pose2d': (pose2d / s)[None],
+                'visibility': vis[None], 'heatmaps': heat[None], 'centermaps': centermap[None],
+                'exception': np.array([self.exception])}
+
+
+READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq, 'MHP_mv': MHP_mv, 'MHP_CPM_kpt': MHP_CPM_kpt}
+CPM_KEYS = ('heatmaps', 'centermaps', 'exception')
 
 
 def decode(path, bgr):
@@ -417,6 +498,9 @@ def collate(samples, bgr=False):
     for k in MULTI_VIEW_KEYS:                          # MHP_mv: one entry per sample, stacked to (B, ...) float64
         if k in samples[0]:
             out[k] = torch.from_numpy(np.stack([np.asarray(s[k], dtype=np.float64) for s in samples]))
+    for k in CPM_KEYS:                                 # MHP_CPM_kpt: per image, stacked like the labels
+        if k in samples[0]:
+            out[k] = torch.from_numpy(np.concatenate([s[k] for s in samples]))
     return out
 
 

@@ -312,7 +312,13 @@ class RHDLoader(object):
         buf = stage.to(dev, non_blocking=True)
         self._copied[k] = torch.cuda.Event()
         self._copied[k].record()
-        out = {'imgs': affine_warp_normalize(buf, b['table'], b['inverse'], self.size)}
+        if getattr(self.dataset, 'resize', False):
+            # a reader of whole frames resized to (width, height) with its own normalisation (dataset/mhp.py MHP_CPM_kpt)
+            from dataset.preprocess import resize_normalize
+            out = {'imgs': resize_normalize(buf, b['table'], (self.dataset.width, self.dataset.height),
+                                            mean=self.dataset.mean, std=self.dataset.std)}
+        else:
+            out = {'imgs': affine_warp_normalize(buf, b['table'], b['inverse'], self.size)}
         if self.heatmaps:
             joints = torch.cat((b['pose2d'], b['visibility'].float()), 2).pin_memory().to(dev, non_blocking=True)
             out['heatmaps'] = HeatmapGenerator(self.hm_res, self.num_joints, self.sigma)(joints)

@@ -41,3 +41,18 @@ def get_final_preds(hms, use_softmax=True):
     preds = torch.empty((b, k, 2), dtype=torch.float32, device=hms.device)
     C.call('hrnet_decode_argmax', hms.detach().data_ptr(), preds.data_ptr(), None, b * k, h, w, 0, C.stream_ptr())
     return preds
+
+
+def decode_argmax(hms):
+    """hms: B x K x H x W on the HIP device -> B x K x 2 [u right, v down] float: the first arg-max of the flattened map
+    (torch.argmax's tie rule) with u = idx % W, v = idx // W, the get_kpts of the reference's CPM reader
+    (lib/dataset/MHP_CPMDataset.py:252-262). hrnet_decode_argmax's plain style takes both from its first size
+    argument, so the map is handed over as W x H: the flat index is the same."""
+    if not isinstance(hms, torch.Tensor) or hms.ndim != 4 or not hms.is_cuda:
+        raise ValueError('decode_argmax: expected a (B, K, H, W) HIP-device tensor (no CPU path in this build)')
+    hms = hms.detach().contiguous().float()
+    b, k, h, w = hms.shape
+    preds = torch.empty((b, k, 2), dtype=torch.float32, device=hms.device)
+    with torch.cuda.device(hms.device):
+        C.call('hrnet_decode_argmax', hms.data_ptr(), preds.data_ptr(), None, b * k, w, h, 0, C.stream_ptr())
+    return preds

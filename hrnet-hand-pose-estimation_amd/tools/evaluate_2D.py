@@ -12,7 +12,9 @@ coordinates are rescaled to original-image pixels with `* crop_size / hm_size + 
 (dataset/mhp.py: MHP, MHP_kpt, MHP_seq) serve <DATA_DIR>/MHP; their batches carry `hm_inverse`, the inverse of each
 sample's heat-map matrix, and the coordinates are mapped back through it. The reference scales MHP by 640/64 and
 480/64 instead (:241-245), which does not invert its own 'short'-scale crop of the frame. With MODEL.NAME
-pose_hrnet_transformer on MHP_seq the poses evaluated are the model's refined poses of the centre frames.
+pose_hrnet_transformer on MHP_seq the poses evaluated are the model's refined poses of the centre frames. With MODEL.NAME
+CPM (MHP_CPM_kpt) the model takes the batch's `centermaps` as well, and the key points are the integer arg-max of the last
+stage's map without its background channel (reference :184-189), mapped back to the frame through `hm_inverse`.
 """
 import argparse
 import os
@@ -25,8 +27,8 @@ import torch
 from config import cfg, update_config
 from core.evaluate2d import Eval2DAccumulator, load_checkpoint_state
 from dataset.build import make_dataloader
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401
-from utils.heatmap_decoding import get_final_preds
+from models import CPM, pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401
+from utils.heatmap_decoding import decode_argmax, get_final_preds
 
 
 def parse_args():
@@ -74,6 +76,10 @@ def main():
             if cfg.MODEL.NAME == 'pose_hrnet_transformer':
                 # MHP_seq's frame-major window batch -> the refined poses of the centre frames, (4 B, K, 2)
                 pred = model(imgs, frames=len(cfg.DATASET.SEQ_IDX))[0]
+            elif cfg.MODEL.NAME == 'CPM':
+                # the last stage's map without its background channel, decoded by integer argmax (the reference's
+                # get_kpts, evaluate_2D.py:184-189); MHP_CPM_kpt's hm_inverse maps the stride-8 pixels to the frame
+                pred = decode_argmax(model(imgs, ret['centermaps'].to(device))[-1][:, 1:])
             else:
                 hm = model(imgs)[0]      # (heatmaps, inter_feat[, temperature])
                 pred = get_final_preds(hm, cfg.MODEL.HEATMAP_SOFTMAX)

@@ -24,7 +24,7 @@ from config import cfg, update_config
 from core.function import train, validate
 from core.loss import BoneLengthLoss, HeatmapLoss, JointAngleLoss, JointsMSELoss
 from dataset.build import make_dataloader
-from models import pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401  (dispatched by name below)
+from models import CPM, pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401  (dispatched by name below)
 from utils.utils import create_logger, get_optimizer, save_checkpoint
 
 
@@ -68,6 +68,10 @@ def check_config(cfg):
         raise ValueError('MODEL.NAME pose_hrnet_hamburger: {} (no SyncBN batch statistics, no backward through the NMF, no '
                          'Dropout2d); evaluation works: tools/evaluate_2D.py and tools/inference.py run it'.format(
                              pose_hrnet_hamburger.NOT_BUILT))
+    if cfg.MODEL.NAME == 'CPM':
+        raise ValueError('MODEL.NAME CPM: {} (no backward of the K x K convolution and the pools, no six-stage heat-map '
+                         'loss, no training transforms in MHP_CPM_kpt); evaluation works: tools/evaluate_2D.py runs '
+                         'it'.format(CPM.NOT_BUILT))
 
 
 def main():

@@ -1308,6 +1308,31 @@ int hrnet_modulated_deform_conv_backward(const float* input, const float* offset
                                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                                          int groups, int deformable_groups, hr_stream_t stream);
 
+/*
+ * K x K convolution of the Convolutional Pose Machine (nn.Conv2d of lib/models/CPM.py:11-66: 5x5, 9x9, 11x11 and 1x1
+ * layers with bias, F.relu behind most of them): f32 NHWC, odd ks <= 11, stride 1, padding ks/2, implicit GEMM on the
+ * f32 MFMA (csrc/conv_kxk.hip). hrnet_conv2d above serves ks 1 and 3 only.
+ *   x     [N,H,W,ldx]; the Cin input channels are [x_off, x_off + Cin) of each pixel (Cin, ldx, x_off multiples of 4)
+ *   w     hrnet_pack_weights mode 0 in HR_F32: [Cout rounded up to 16][ks*ks][Cin]
+ *   bias  optional [Cout] f32; relu 1: y = max(y, 0)
+ *   y     [N,H,W,ldy]; the Cout output channels are [y_off, y_off + Cout) of each pixel, any Cout >= 1. Nothing outside
+ *         that slice is written: a producer writes its part of a concatenated map (CPM.py:91) in place.
+ * dtype: HR_F32 only. The summation order is fixed and independent of N (csrc/conv_kxk.hip states it): two launches give
+ * equal bits. Anything else (even ks, ks > 11, alignment, a slice outside ld) is HR_E_BADARG and writes nothing.
+ */
+int hrnet_conv2d_kxk(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Cin,
+                     int ldx, int x_off, int Cout, int ldy, int y_off, int ks, int relu, hr_stream_t stream);
+/* constants of that kernel: which 0 = pixel-tile height, 1 = pixel-tile width, 2 = input channels staged per pass,
+ * 3 = largest ks; anything else 0 */
+hr_value_t hrnet_conv_kxk_tile(int which);
+/* nn.MaxPool2d(3, 2, 1) (CPM.py:12-27) on f32 NHWC: x [N,H,W,ldx] channels [x_off, x_off + C) -> y [N,Ho,Wo,ldy] channels
+ * [y_off, y_off + C), Ho = (H-1)/2 + 1, Wo = (W-1)/2 + 1; the padding never wins (-inf semantics) */
+int hrnet_maxpool2d_3x3s2(const float* x, float* y, int N, int H, int W, int C, int ldx, int x_off, int ldy, int y_off,
+                          hr_stream_t stream);
+/* nn.AvgPool2d(9, 8, 1) of the centre map (CPM.py:10; count_include_pad: always / 81): x [N,1,H,W] f32 -> channel y_off
+ * of y [N,Ho,Wo,ldy], Ho = (H-7)/8 + 1, Wo = (W-7)/8 + 1; H, W >= 7 (torch refuses a smaller map as well) */
+int hrnet_avgpool2d_9s8(const float* x, float* y, int N, int H, int W, int ldy, int y_off, hr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
