@@ -54,6 +54,8 @@ _DEFAULTS = dict(
         PROCESS_FEATURE_LR=0.001, VOLUME_NET_LR=0.001, OPTIMIZER='adam', BN_MOMENTUM=3e-4, MOMENTUM=0.9,
         WD=0.0001, NESTEROV=False, GAMMA1=0.99, GAMMA2=0.0, BEGIN_EPOCH=0, END_EPOCH=140, RESUME=False,
         CHECKPOINT='', IMAGES_PER_GPU=32, SHUFFLE=True,
+        # MI355X build: the six stage weights of CPM's loss (tools/train_cpm.py); the reference supervises the last stage
+        CPM_STAGE_WEIGHTS=[0.0, 0.0, 0.0, 0.0, 0.0, 1.0],
     ),
     TEST=dict(
         IMAGES_PER_GPU=32, FLIP_TEST=False, POST_PROCESS=False, SHIFT_HEATMAP=False, USE_GT_BBOX=False,

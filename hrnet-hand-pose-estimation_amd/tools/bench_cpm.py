@@ -11,6 +11,14 @@ inside one loop; medians with the spread (min .. max) over the repeats, and the 
 the f32 MFMA reaches on this device. The yardstick is always torch's op in the same run, never an earlier run of this
 kernel. Lines are appended to profiles/cpm_times.txt. Without a HIP device the timing mode fails: there is no fallback.
 
+    python tools/bench_cpm.py --train [--batches 1 16]   (the training step and the dominant layers' gradients)
+
+--train measures the training step of models.CPM(trainable=True) - forward, last-stage loss, backward, FlatAdam - against
+torch autograd + torch.optim.Adam on the same weights, and hrnet_conv2d_kxk_wgrad / _dgrad of the same three layers
+against torch.nn.grad.conv2d_weight / conv2d_input (MIOpen, f32), in the same run: medians of 10 after 3 warm-ups,
+appended to profiles/cpm_train_times.txt. `train_counts(B)` is its cost model: three times the forward's FLOPs, minus the
+image layers' data gradient. --train --counts-only prints it without a device.
+
 `counts(B)` is the cost model: per layer the launches of one forward, 2 * MACs, and the bytes of weights and
 activations.
 """
@@ -56,6 +64,100 @@ def counts(B, size=SIZE, k=JOINTS):
     total['launches'] += 8
     total['mfma_floor_us'] = 1e6 * total['flops'] / F32_MFMA_FLOPS
     return {'layers': layers, 'total': total}
+
+
+def train_counts(B, size=SIZE, k=JOINTS):
+    """FLOPs of one training step: the forward, the weight gradient (as many MACs again) and the data gradient (again as
+    many, except for the two image layers, whose input needs none)"""
+    c = counts(B, size, k)
+    layers = {}
+    for name, ci, co, ks, side in layer_sizes(size, k):
+        f = c['layers'][name]['flops']
+        layers[name] = {'forward': f, 'wgrad': f, 'dgrad': 0 if ci == 3 else f}
+    total = {key: sum(row[key] for row in layers.values()) for key in ('forward', 'wgrad', 'dgrad')}
+    total['flops'] = total['forward'] + total['wgrad'] + total['dgrad']
+    total['mfma_floor_us'] = 1e6 * total['flops'] / F32_MFMA_FLOPS
+    return {'layers': layers, 'total': total}
+
+
+def measure_train(B, repeats, warmup):
+    """the training step (forward, last-stage loss, backward, Adam) of models.CPM(trainable=True) against torch autograd on
+    the same weights, and the weight and data gradients of the three dominant layers against torch.nn.grad (MIOpen, f32),
+    the two paths alternating inside one loop"""
+    import torch
+    import torch.nn.functional as F
+    from hipnet import conv_kxk_train as T
+    from hipnet.optim import FlatAdam
+    from models import CPM
+    torch.manual_seed(0)
+    model = CPM.CPM(JOINTS, trainable=True)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name.endswith('.weight'):
+                p.normal_(0.0, (2.0 / (p.shape[1] * p.shape[2] * p.shape[3])) ** 0.5)
+            else:
+                p.normal_(0.0, 0.1)
+    model = model.cuda().train()
+    P = {k: v.detach().clone().requires_grad_(True) for k, v in model.named_parameters()}
+    g = torch.Generator(device='cuda').manual_seed(1)
+    image = torch.randn(B, 3, SIZE, SIZE, device='cuda', generator=g) * 0.5
+    yy, xx = torch.meshgrid(torch.arange(SIZE, device='cuda'), torch.arange(SIZE, device='cuda'), indexing='ij')
+    center = torch.exp(-((xx - 130.0) ** 2 + (yy - 120.0) ** 2) / 18.0)[None, None].repeat(B, 1, 1, 1).contiguous()
+    target = torch.rand(B, JOINTS + 1, SIZE // 8, SIZE // 8, device='cuda', generator=g)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    opt_hip, opt_torch = FlatAdam(model, lr=1e-4), torch.optim.Adam(list(P.values()), lr=1e-4)
+
+    def step_hip():
+        opt_hip.zero_grad()
+        CPM.cpm_loss(model(image, center), target).backward()
+        opt_hip.step()
+
+    def step_torch():
+        opt_torch.zero_grad()
+        (((torch_forward(P, image, center)[-1] - target) ** 2).sum((2, 3)).mean()).backward()
+        opt_torch.step()
+
+    jobs = {'step_hip': step_hip, 'step_torch': step_torch}
+    sizes = {n: (ci, co, ks, side) for n, ci, co, ks, side in layer_sizes()}
+    for name, _ in DOMINANT:
+        ci, co, ks, side = sizes[name]
+        cip = (ci + 3) // 4 * 4
+        x_nchw = torch.randn(B, ci, side, side, device='cuda', generator=g)
+        dy_nchw = torch.randn(B, co, side, side, device='cuda', generator=g)
+        x_nhwc = torch.zeros(B, side, side, cip, device='cuda')
+        x_nhwc[..., :ci] = x_nchw.permute(0, 2, 3, 1)
+        dy_nhwc = dy_nchw.permute(0, 2, 3, 1).contiguous()
+        w = P[name + '.weight'].detach()
+        scratch = torch.empty(T.wgrad_plan(B, side, side, cip, co, ks)[0] // 4, device='cuda')
+        dw, db = torch.empty_like(w), torch.empty(co, device='cuda')
+        jobs[name + '_wgrad_hip'] = lambda x=x_nhwc, dy=dy_nhwc, s=scratch, dw=dw, db=db, cip=cip, ci=ci, co=co, ks=ks: \
+            T.wgrad(x, dy, s, dw, db, cip, ci, 0, co, 0, ks)
+        jobs[name + '_wgrad_torch'] = lambda x=x_nchw, dy=dy_nchw, w=w, ks=ks: \
+            (torch.nn.grad.conv2d_weight(x, w.shape, dy, padding=ks // 2), dy.sum((0, 2, 3)))
+        if ci != 3:
+            wt = T.pack_dgrad(w, co)
+            dx = torch.empty(B, side, side, ci, device='cuda')
+            jobs[name + '_dgrad_hip'] = lambda dy=dy_nhwc, wt=wt, dx=dx, ci=ci, co=co, ks=ks: \
+                T.dgrad(dy, wt, dx, None, co, 0, ci, 0, 0, ks, False)
+            jobs[name + '_dgrad_torch'] = lambda x=x_nchw, dy=dy_nchw, w=w, ks=ks: \
+                torch.nn.grad.conv2d_input(x.shape, w, dy, padding=ks // 2)
+    times = {}
+    for r in range(warmup + repeats):
+        for label, fn in jobs.items():
+            t = _time(fn, start, stop)
+            if r >= warmup:
+                times.setdefault(label, []).append(t)
+    out = {k: {'median_us': statistics.median(v), 'min_us': min(v), 'max_us': max(v)} for k, v in times.items()}
+    c = train_counts(B)
+    for k, v in out.items():
+        what = k.rsplit('_', 1)[0]
+        flops = c['total']['flops'] if what == 'step' else c['layers'][what.rsplit('_', 1)[0]]['wgrad']
+        v['tflops'] = flops / v['median_us'] / 1e6
+    with torch.no_grad():
+        gh = {k: p.grad for k, p in model.named_parameters()}
+        out['relative_difference_of_the_last_gradients'] = max(
+            float((gh[k] - P[k].grad).abs().max() / P[k].grad.abs().max().clamp_min(1e-30)) for k in P)
+    return out
 
 
 def torch_forward(P, image, center):
@@ -148,17 +250,45 @@ def measure(B, repeats, warmup):
     return out
 
 
+def main_train(args):
+    repeats = 10 if args.repeats == 20 else args.repeats
+    lines = []
+    for B in args.batches:
+        row = {'B': B, 'train_counts': train_counts(B)}
+        if not args.counts_only:
+            row['times'] = t = measure_train(B, repeats, args.warmup)
+            for name in sorted({k.rsplit('_', 1)[0] for k in t if k.endswith('_hip')}):
+                h, o = t[name + '_hip'], t[name + '_torch']
+                row[name + '_ratio_torch_over_hip'] = o['median_us'] / h['median_us']
+                lines.append('B {:3d}  {:20s} hip {:.0f} ({:.0f} .. {:.0f}) us {:.1f} TF ({:.0f} % of 155)  torch {:.0f} '
+                             '({:.0f} .. {:.0f}) us {:.1f} TF  torch / hip {:.2f}'.format(
+                                 B, name, h['median_us'], h['min_us'], h['max_us'], h['tflops'], 100 * h['tflops'] / 155,
+                                 o['median_us'], o['min_us'], o['max_us'], o['tflops'], o['median_us'] / h['median_us']))
+        print(json.dumps(row))
+    if lines:
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'profiles',
+                            'cpm_train_times.txt')
+        with open(path, 'a') as f:
+            f.write('bench_cpm.py --train: median (min .. max) of {} after {} warm-ups\n'.format(repeats, args.warmup) +
+                    '\n'.join(lines) + '\n')
+        print('\n'.join(lines))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 16])
     ap.add_argument('--repeats', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--counts-only', action='store_true')
+    ap.add_argument('--train', action='store_true', help='the training step and the gradients of the dominant layers '
+                    '(medians of 10 after 3 warm-ups unless --repeats / --warmup say otherwise)')
     args = ap.parse_args(argv)
     if not args.counts_only:
         import torch
         if not torch.cuda.is_available():
             sys.exit('bench_cpm: no HIP device: the timings need one (--counts-only prints the cost model)')
+    if args.train:
+        return main_train(args)
     lines = []
     for B in args.batches:
         row = {'B': B, 'counts': counts(B)}

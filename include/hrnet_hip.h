@@ -1333,6 +1333,45 @@ int hrnet_maxpool2d_3x3s2(const float* x, float* y, int N, int H, int W, int C, 
  * of y [N,Ho,Wo,ldy], Ho = (H-7)/8 + 1, Wo = (W-7)/8 + 1; H, W >= 7 (torch refuses a smaller map as well) */
 int hrnet_avgpool2d_9s8(const float* x, float* y, int N, int H, int W, int ldy, int y_off, hr_stream_t stream);
 
+/*
+ * Training of the Convolutional Pose Machine (csrc/conv_kxk_train.hip): the backward of hrnet_conv2d_kxk and of
+ * hrnet_maxpool2d_3x3s2. f32 NHWC, channel slices as above, no atomics, a fixed summation order (stated at the top of the
+ * source file): two runs from the same state give equal bits. Anything an entry cannot serve is HR_E_BADARG before
+ * the first launch, and nothing is written.
+ *
+ * conv2d_kxk_wgrad_scratch: pure host query: *bytes of scratch and *nsplit pixel-tile splits that conv2d_kxk_wgrad uses
+ *   for this shape and, if split_tiles != NULL, the 8 x 16 pixel tiles of one split (the last one holds what is left).
+ *   A function of the shape alone (csrc/conv_kxk_split.h).
+ * conv2d_kxk_wgrad: dw[co][ci][r][s] = sum_{n,h,w} dy[n,h,w,co] x[n,h+r-p,w+s-p,ci], p = ks/2, in the Conv2d layout
+ *   (Cout, Cin_real, ks, ks), overwritten; db (optional) [Cout] = sum_{n,h,w} dy.
+ *   x   [N,H,W,ldx] read at channels [x_off, x_off + Cin) (Cin, ldx, x_off multiples of 4, x 16-byte aligned); only the
+ *       first Cin_real <= Cin of them have a gradient (the image layers' fourth channel and the concatenated map's pad
+ *       are never written). Cin == 4 runs an arrangement of its own (four taps x four channels per MFMA).
+ *   dy  [N,H,W,ldy] read at channels [y_off, y_off + Cout), any Cout >= 1, any offset.
+ *   scratch: the partial sums of the splits, at least *bytes of the query; a second launch adds them in split order.
+ * conv2d_kxk_dgrad: dx[n,h,w,ci] = sum_{co,r,s} dy[n,h-r+p,w-s+p,co] w[co][ci][r][s] as the forward convolution of dy on
+ *   the forward's own tile body:
+ *   dy  [N,H,W,ldy] read at [y_off, y_off + Cout): Cout, ldy, y_off multiples of 4 (pad channels of dy hold zeros)
+ *   wT  hrnet_pack_weights mode 0 of the weight permuted to (Cin, Cout, ks, ks) and flipped in both kernel axes:
+ *       [Cin rounded up to 16][ks*ks][Cout]
+ *   dx  [N,H,W,ldx] written at [x_off, x_off + Cin), any Cin >= 1, nothing else touched
+ *   mask optional [N,H,W,ldm] read at [m_off, m_off + Cin): the result is zeroed where mask <= 0 (the ReLU of the layer
+ *       that produced this input: its saved output); accumulate 1: the (masked) result is added onto what dx holds.
+ * maxpool2d_3x3s2_bwd: dx[n,h,w,c] = sum of dy over the windows whose arg-max (h, w) is - the forward's rule: first
+ *   maximum in (dh, dw) scan order, padding skipped, a NaN wins; relu_mask 1: times (x > 0), the backward of the ReLU
+ *   that produced x. x [N,H,W,ldx] at x_off, dy [N,Ho,Wo,lddy] at dy_off, dx [N,H,W,lddx] at dx_off (overwritten).
+ */
+int hrnet_conv2d_kxk_wgrad_scratch(int dtype, int N, int H, int W, int Cin, int Cout, int ks, HR_HOST long long* bytes,
+                                   HR_HOST int* nsplit, HR_HOST long long* split_tiles);
+int hrnet_conv2d_kxk_wgrad(int dtype, const void* x, const void* dy, void* scratch, long long scratch_bytes, float* dw,
+                           float* db, int N, int H, int W, int Cin, int Cin_real, int ldx, int x_off, int Cout, int ldy,
+                           int y_off, int ks, hr_stream_t stream);
+int hrnet_conv2d_kxk_dgrad(int dtype, const void* dy, const void* wT, void* dx, const float* mask, int N, int H, int W,
+                           int Cout, int ldy, int y_off, int Cin, int ldx, int x_off, int ldm, int m_off, int ks,
+                           int accumulate, hr_stream_t stream);
+int hrnet_maxpool2d_3x3s2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, int ldx, int x_off,
+                              int lddy, int dy_off, int lddx, int dx_off, int relu_mask, hr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
