@@ -1372,6 +1372,41 @@ int hrnet_conv2d_kxk_dgrad(int dtype, const void* dy, const void* wT, void* dx, 
 int hrnet_maxpool2d_3x3s2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, int ldx, int x_off,
                               int lddy, int dy_off, int lddx, int dx_off, int relu_mask, hr_stream_t stream);
 
+/*
+ * The head of FTLMultiviewNet (lib/models/FTL_encoder_decoder.py; csrc/ftl.hip), f32 NHWC, inference.
+ *
+ * The feature transform layer reads a map per channel as 3-vectors: triplets of consecutive pixels in row-major order
+ * (H W a multiple of 3; a triplet may cross a row boundary), and maps each by an affine x -> x A + c of its view.
+ * coef: device [B V][12] f32, A row-major (9) then c (3), slot b V + v. Each output is
+ * fma(x2, A[2][j], fma(x1, A[1][j], fma(x0, A[0][j], c[j]))) in that order.
+ * ftl_gather:  x [B V,H,W,ldx] channels [x_off, x_off + C) -> y [B,H,W,ldy], view v into channels
+ *   [y_off + v slice, y_off + v slice + C): the concatenation over the views is written in place. Channels of a slice past
+ *   C are not written.
+ * ftl_scatter: f [B,H,W,ldf] channels [f_off, f_off + C) -> y [B V,H,W,ldy] channels [y_off, y_off + C), slot b V + v, all
+ *   V views from one read of f.
+ * C, slice, every ld and offset are multiples of 4 and the maps 16-byte aligned; a slice outside its row, or H W no
+ * multiple of 3, is HR_E_BADARG and nothing is written.
+ *
+ * conv2d_3x3g: a 3x3 convolution with an explicit output size, implicit GEMM on the f32 MFMA:
+ *   y[n,ho,wo,co] = relu?(bias[co] + sum_{r,s,ci} w[co][3 r + s][ci] xz[n, ho stride + r - pad_lo, wo stride + s - pad_lo, ci])
+ *   xz[i] = x[i / z] when i % z == 0 and 0 <= i / z < H (W), else 0
+ * stride 1 or 2, pad_lo 0 .. 2, z 1 or (with stride 1) 2. Conv2d(3, stride 2, padding 2) is (2, 2, 1) with
+ * Ho = (H + 1) / 2 + 1; ConvTranspose2d(3, stride 2, padding 2, output_padding op) is (1, 0, 2) with Ho = 2 H - 3 + op on the
+ * flipped, transposed weight (hrnet_pack_weights mode 1); for z = 2 only the taps that meet no stuffed zero are issued.
+ *   x [N,H,W,ldx] read at [x_off, x_off + Cin) (Cin, ldx, x_off multiples of 4); w [Cout rounded up to 16][9][Cin];
+ *   bias optional [Cout]; y [N,Ho,Wo,ldy] written at [y_off, y_off + Cout), any Cout >= 1, nothing else touched.
+ *   Ho must lie between the output size with no padding behind the (stuffed) map and that with two rows of it, Wo
+ *   likewise: anything else is HR_E_BADARG. dtype: HR_F32 only. The summation order is fixed and independent of N
+ *   (csrc/ftl.hip states it).
+ */
+int hrnet_ftl_gather(const float* x, const float* coef, float* y, int B, int V, int H, int W, int C, int ldx, int x_off,
+                     int ldy, int y_off, int slice, hr_stream_t stream);
+int hrnet_ftl_scatter(const float* f, const float* coef, float* y, int B, int V, int H, int W, int C, int ldf, int f_off,
+                      int ldy, int y_off, hr_stream_t stream);
+int hrnet_conv2d_3x3g(int dtype, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int Cin,
+                      int ldx, int x_off, int Cout, int ldy, int y_off, int Ho, int Wo, int stride, int pad_lo, int z,
+                      int relu, hr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
