@@ -1,7 +1,8 @@
 """FTLMultiviewNet, MODEL.NAME `FTL` (reference lib/models/FTL_encoder_decoder.py:83-214): a multi-view encoder-decoder
 on the 480-channel features of the frozen pose_hrnet_softmax backbone. The encoded map of every view is read as 3-vectors,
 carried into a common world frame by that view's camera (the feature transform layer), fused over the views, carried back
-into every view's frame and decoded to heat maps; the decoded 2-D points are lifted by DLT. Inference only.
+into every view's frame and decoded to heat maps; the decoded 2-D points are lifted by DLT. Inference by default; the
+head trains when the model is built with trainable=True (the backbone stays frozen, as in the reference's train3D.py).
 
 forward(images (B, V, 3, H, W), extrinsic_matrices (B, V, 3, 4) = [R | t], intrinsic_matrices (3, 3) or (B, 3, 3),
         to_frame=None, orig_img_size=(640, 480))
@@ -56,8 +57,28 @@ Reference defects not reproduced:
 
 Refused when the model is built: a MODEL.BACKBONE_NAME other than 'pose_hrnet_softmax', MODEL.COMPUTE_DTYPE other than
 fp32, a C with C / 2 no multiple of 4, DATASET.NUM_VIEWS < 1. Refused in forward: CPU tensors (ValueError), a number of
-views other than DATASET.NUM_VIEWS, features whose encoded h2 w2 is no multiple of 3, training mode and eval mode with a
-gradient required (NotImplementedError - run model.eval() under torch.no_grad()). Training the head is not built.
+views other than DATASET.NUM_VIEWS, features whose encoded h2 w2 is no multiple of 3, and - for a model built without
+trainable=True - training mode and eval mode with a gradient required (NotImplementedError - run model.eval() under
+torch.no_grad()).
+
+Training (FTLMultiviewNet(config, is_train, trainable=True), model.train(), gradients enabled): the head runs on batch
+statistics as ONE autograd node (hipnet.ftl_train.HeadFn), from the features and cameras to the heat maps and from the
+heat maps' gradient to .grad of every head parameter, with no torch convolution in between:
+  conv + BatchNorm + ReLU   the raw-weight convolution with its bias and no ReLU (the kernels above), then
+                            nhwc.bn_batch_forward, which updates the running statistics with the module's momentum;
+                            backward nhwc.bn_batch_backward (gamma, beta and the convolution's bias), then
+  weight gradients          hrnet_conv2d_3x3g_wgrad for the strided layers and - with the roles of input and gradient
+                            swapped - the transposed ones; hrnet_conv2d_kxk_wgrad (ks 1, and ks 3 for the output layer)
+  data gradients            the forward kernel hrnet_conv2d_3x3g itself on repacked weights (hipnet.ftl_train states the
+                            two identities), hrnet_conv2d_kxk_dgrad for the 1x1 layers and the output layer,
+                            hrnet_ftl_scatter_bwd / hrnet_ftl_gather_bwd for the transforms; encoder_head.0 needs none
+  output layer              decoder.layer_lst.2 and final_layer stay folded (nothing lies between them, so the fold is exact
+                            in training): W_out = Wf W_last and b_out are formed on the device each step, dW_out / db_out
+                            come from hrnet_conv2d_kxk_wgrad and go back through the product: dWf = <dW_out, W_last>,
+                            dW_last = Wf^T dW_out, db_last = Wf^T db_out, db_fin = db_out
+pose2d_pred and pose3d_pred then come from the differentiable expectation decode and DLT. The backbone runs in eval mode
+under no_grad. model.hip() hands hipnet.optim.FlatAdam the flat parameters and gradients of the head; a backward pass
+overwrites the gradients. Under torch.no_grad(), or in .eval(), a trainable model runs the inference path bit for bit.
 """
 import logging
 
@@ -66,6 +87,7 @@ import torch.nn as nn
 
 from hipnet import conv_kxk as KX
 from hipnet import ftl as FT
+from hipnet import ftl_train as FTT
 from hipnet import nhwc
 from utils.heatmap_decoding import get_final_preds
 from utils.multiview import triangulate_batch_of_points
@@ -133,9 +155,11 @@ def _fold(bn):
 
 
 class FTLMultiviewNet(nn.Module):
-    def __init__(self, config, is_train=False):
+    def __init__(self, config, is_train=False, trainable=False):
         super(FTLMultiviewNet, self).__init__()
         check_config(config)
+        self.trainable = bool(trainable)
+        self._flat, self._dirty, self.tape = None, 0, None
         M = config.MODEL
         from models import pose_hrnet_softmax
         self.backbone = pose_hrnet_softmax.get_pose_net(config, is_train=True)
@@ -166,7 +190,7 @@ class FTLMultiviewNet(nn.Module):
     def _head_plan(self):
         """per layer (packed weights with the BatchNorm scale folded in, bias with its shift); built once, rebuilt when a
         head parameter or buffer was written or moved"""
-        key = tuple((t.data_ptr(), t._version) for t in self._head_tensors())
+        key = tuple((t.data_ptr(), t._version) for t in self._head_tensors()) + (self._dirty,)
         if self._plan is not None and key == self._plan_key:
             return self._plan
 
@@ -200,8 +224,37 @@ class FTLMultiviewNet(nn.Module):
         self._plan_key = key
         return self._plan
 
+    # ---- training --------------------------------------------------------------------------------------------------
+    def hip(self):
+        """the flat f32 parameter and gradient buffers of the head (what hipnet.optim.FlatAdam steps): built on first use
+        on the parameters' device; every head parameter becomes a view of flat_p and its .grad a view of flat_g"""
+        if not self.trainable:
+            raise NotImplementedError('FTLMultiviewNet: {}: build the model with trainable=True'.format(NOT_BUILT))
+        if self._flat is None or self._flat.flat_p.device != self.final_layer.weight.device:
+            self._flat = FTT.HeadFlat(self)
+        return self._flat
+
+    def head_parameters(self):
+        return [p for m in FTT.HEAD_MODULES for p in getattr(self, m).parameters()]
+
+    def train(self, mode=True):
+        super(FTLMultiviewNet, self).train(mode)
+        if self.trainable:
+            self.backbone.eval()           # frozen: its BatchNorms keep their running statistics
+        return self
+
+    def _training_pass(self):
+        return self.trainable and self.training and torch.is_grad_enabled()
+
     # ---- the model -------------------------------------------------------------------------------------------------
     def _refuse(self, x):
+        if self.trainable:
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise ValueError('FTLMultiviewNet: expected HIP-device tensors (there is no CPU path in this build)')
+            if self.final_layer.weight.device != x.device:
+                raise ValueError('FTLMultiviewNet: the model is on {} and the input on {}: move the model with '
+                                 '.cuda()'.format(self.final_layer.weight.device, x.device))
+            return
         if self.training:
             raise NotImplementedError('FTLMultiviewNet: {} (the backward of the transforms and of the general 3x3 '
                                       'convolution is the next step): call .eval() and run under '
@@ -270,13 +323,29 @@ class FTLMultiviewNet(nn.Module):
             hm = nhwc.heatmap_softmax(logits, K, p['temp'])
         return {'encoder_head': enc, 'fuse_after_FTL': fused, 'channel_expansion': exp, 'logits': logits, 'heatmaps': hm}
 
+    def _head_train(self, features, extrinsic_matrices, intrinsic_matrices):
+        """the training forward of the head on batch statistics: heat maps (B V, K, h, w) that carry the head's backward"""
+        self._refuse(features)
+        if features.ndim != 4 or features.shape[1] != self.in_channel or features.numel() == 0:
+            raise ValueError('features {}: expected (B * V, {}, h, w)'.format(tuple(features.shape), self.in_channel))
+        self._cameras(extrinsic_matrices, features.shape[0])
+        h2, w2 = self.encoded_size(features.shape[2], features.shape[3])
+        if (h2 * w2) % 3:
+            raise ValueError('features {}: the encoded map is {} x {} = {} pixels, no whole number of triplets'.format(
+                tuple(features.shape), h2, w2, h2 * w2))
+        return FTT.head_forward_train(self, features, extrinsic_matrices, intrinsic_matrices)
+
     def head_forward(self, features, extrinsic_matrices, intrinsic_matrices, to_frame=None, orig_img_size=(640, 480)):
         """features (B * V, C, h, w) NCHW on the device, slot order b V + v -> (heatmaps_pred, pose2d_pred, pose3d_pred):
         everything after the backbone"""
-        hm = self.head_stages(features, extrinsic_matrices, intrinsic_matrices)['heatmaps']
+        train = self._training_pass()
+        if train:
+            hm = self._head_train(features, extrinsic_matrices, intrinsic_matrices)
+        else:
+            hm = self.head_stages(features, extrinsic_matrices, intrinsic_matrices)['heatmaps']
         B, V, K = extrinsic_matrices.shape[0], self.num_views, self.num_joints
         dev = hm.device
-        with torch.no_grad():
+        with torch.enable_grad() if train else torch.no_grad():
             pose2d = get_final_preds(hm, True).view(B, V, K, 2)
             Kmat = intrinsic_matrices.to(dev).double()
             Kmat = Kmat[0] if Kmat.ndim == 3 else Kmat

@@ -4,6 +4,7 @@ same device with the same weights:
 
     python tools/bench_ftl.py [--batches 1 4] [--views 4] [--repeats 20] [--warmup 3]
     python tools/bench_ftl.py --counts-only          (no device: launches, FLOPs issued and useful, bytes per stage)
+    python tools/bench_ftl.py --train [--counts-only]  (the head's training step: forward on batch statistics + backward)
 
 It times the whole head (features in, heat maps out) and its three dominant layers alone - encoder_head.0 (Conv2d 3x3
 stride 2 padding 2, 480 -> 480, 64 -> 33), decoder.0 (ConvTranspose2d 480 -> 256, 18 -> 33) and decoder.1 (ConvTranspose2d
@@ -14,6 +15,14 @@ is compared is kernels, not arithmetic tricks. Device events around each call af
 inside one loop; medians with the spread (min .. max) over the repeats, and the achieved TFLOP/s on the USEFUL FLOPs
 against the 155 TF that the f32 MFMA reaches on this device. The yardstick is always torch's op in the same run. Lines
 are appended to profiles/ftl_times.txt. Without a HIP device the timing mode fails: there is no fallback.
+
+--train times the head's forward + backward of a trainable model (hipnet.ftl_train.HeadFn, from the features to the
+gradient of every head parameter, started from a fixed heat-map gradient) against the same head from torch ops under
+autograd (F.conv2d / F.conv_transpose2d / F.batch_norm in training mode, unfolded, torch.autograd.grad to the same
+parameters), whole and per backward stage: the weight gradients of the four 3x3 layers with stride 2
+(hrnet_conv2d_3x3g_wgrad against the weight gradient autograd takes for the same layer), the data gradients that run on
+the forward kernel (against autograd's input gradient) and the two transforms' backward. `train_counts(B, V)` is its
+cost model per backward stage: launches, FLOPs useful, bytes.
 
 `counts(B, V)` is the cost model: per stage the launches, 2 * MACs issued (every MFMA of every workgroup: border pixels
 of the 8 x 16 tiles, padded channels) and useful (real weight times real input), and the bytes of weights and activations.
@@ -89,6 +98,144 @@ def counts(B, V=4, C=CHANNELS, size=SIZE, K=JOINTS):
     return {'stages': rows, 'total': total, 'flops_of_unfused_last_two_layers': unfused}
 
 
+def train_counts(B, V=4, C=CHANNELS, size=SIZE, K=JOINTS):
+    """launches, useful FLOPs and bytes of the head's BACKWARD per stage (host arithmetic). A convolution layer's backward
+    is a weight gradient (2 launches: partials, then their sum in split order) and, but for encoder_head.0, a data
+    gradient (1 launch), each with the useful FLOPs of its forward; a BatchNorm backward is 1 launch over its map, read
+    three times (gradient, input, output) and written once"""
+    fwd = counts(B, V, C, size, K)['stages']
+    rows, total = {}, {'launches': 0, 'flops_useful': 0, 'bytes': 0}
+    for name, kind, N, hin, cin, cout, hout, geo in reversed(stages(B, V, C, size, K)):
+        f = fwd[name]
+        if kind == 't':
+            row = {'launches': 1, 'flops_useful': f['flops_useful'], 'bytes': f['activation_bytes'] + f['weight_bytes']}
+        else:
+            want_dx = name != 'encoder_head.0'
+            last = name == 'decoder.2+final_layer'
+            row = {'launches': 2 + (1 if want_dx else 0) + (0 if last else 1),
+                   'flops_useful': f['flops_useful'] * (2 if want_dx else 1),
+                   'bytes': f['activation_bytes'] * (2 if want_dx else 1) + 2 * f['weight_bytes'] +
+                   (0 if last else 4 * 4 * N * hout * hout * cout)}
+        rows[name] = row
+        for key in total:
+            total[key] += row[key]
+    total['launches'] += 2                                      # softmax backward, layout of the heat-map gradient
+    total['mfma_floor_us'] = 1e6 * total['flops_useful'] / F32_MFMA_FLOPS
+    return {'stages': rows, 'total': total}
+
+
+def torch_train_head(model, feat, coef_g, coef_s, B, V):
+    """the trainable head from torch ops on batch statistics, unfolded, on the model's own parameters"""
+    import torch
+    import torch.nn.functional as F
+
+    def bn(seq, x):
+        return F.relu(F.batch_norm(x, None, None, seq[1].weight, seq[1].bias, True, 0.1, seq[1].eps))
+
+    e, f, d = model.encoder_head.layer_lst, model.fuse_after_FTL.layer_lst, model.decoder.layer_lst
+    x = bn(e[0], F.conv2d(feat, e[0][0].weight, e[0][0].bias, stride=2, padding=2))
+    x = bn(e[1], F.conv2d(x, e[1][0].weight, e[1][0].bias, stride=2, padding=2))
+    C2, h2, w2 = x.shape[1:]
+    trip = x.reshape(B, V, C2, h2 * w2 // 3, 3)
+    Ag, cg = coef_g[..., :9].reshape(B, V, 1, 3, 3), coef_g[..., 9:].reshape(B, V, 1, 1, 3)
+    cat = (torch.matmul(trip, Ag) + cg).reshape(B, V * C2, h2, w2)
+    x = bn(f[0], F.conv2d(cat, f[0][0].weight, f[0][0].bias))
+    x = bn(f[1], F.conv2d(x, f[1][0].weight, f[1][0].bias))
+    As, cs = coef_s[..., :9].reshape(B, V, 1, 3, 3), coef_s[..., 9:].reshape(B, V, 1, 1, 3)
+    x = (torch.matmul(x.reshape(B, 1, C2, h2 * w2 // 3, 3), As) + cs).reshape(B * V, C2, h2, w2)
+    c = model.channel_expansion.layer_lst[0]
+    x = bn(c, F.conv2d(x, c[0].weight, c[0].bias))
+    x = bn(d[0], F.conv_transpose2d(x, d[0][0].weight, d[0][0].bias, stride=2, padding=2))
+    x = bn(d[1], F.conv_transpose2d(x, d[1][0].weight, d[1][0].bias, stride=2, padding=2, output_padding=1))
+    x = F.conv2d(x, d[2].weight, d[2].bias, padding=1)
+    y = F.conv2d(x, model.final_layer.weight, model.final_layer.bias)
+    return F.softmax(y.reshape(y.shape[0], y.shape[1], -1), 2).reshape(y.shape)
+
+
+TRAIN_STAGES = ('encoder_head.0 wgrad', 'encoder_head.1 wgrad', 'decoder.0 wgrad', 'decoder.1 wgrad', 'encoder_head.1 dgrad',
+                'decoder.0 dgrad', 'decoder.1 dgrad', 'transforms bwd')
+
+
+def measure_train(B, V, repeats, warmup):
+    import torch
+    import torch.nn.functional as F
+    from hipnet import ftl, ftl_train
+    model = build_model(V, trainable=True).train()
+    g = torch.Generator(device='cuda').manual_seed(2)
+    feat = torch.randn(B * V, CHANNELS, SIZE, SIZE, device='cuda', generator=g).abs_()
+    ext, K = unit_cameras(B, V, 'cuda')
+    coef_g, coef_s = ftl.affines(ext, K)
+    ghm = torch.randn(B * V, JOINTS, SIZE, SIZE, device='cuda', generator=g)
+    params = model.head_parameters()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    table = {s[0]: s for s in stages(B, V)}
+
+    def step_hip():
+        model._head_train(feat, ext, K).backward(ghm)
+
+    def step_torch():
+        torch.autograd.grad(torch_train_head(model, feat, coef_g, coef_s, B, V), params, ghm)
+
+    step_hip()
+    mine = [p.grad.clone() for p in params]
+    theirs = torch.autograd.grad(torch_train_head(model, feat, coef_g, coef_s, B, V), params, ghm)
+    diff = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(mine, theirs) if a.ndim == 4)
+    jobs = {'step_hip': step_hip, 'step_torch': step_torch}
+    new = lambda *s: torch.randn(*s, device='cuda', generator=g)
+    scratch = torch.empty(1 << 26, device='cuda')
+    for name, transposed in (('encoder_head.0', False), ('encoder_head.1', False), ('decoder.0', True), ('decoder.1', True)):
+        _, _, N, hin, cin, cout, hout, _ = table[name]
+        x = new(N, cin, hin, hin).requires_grad_()
+        w = (new(cin, cout, 3, 3) if transposed else new(cout, cin, 3, 3)).requires_grad_()
+        if transposed:
+            y = F.conv_transpose2d(x, w, stride=2, padding=2, output_padding=hout - (2 * hin - 3))
+        else:
+            y = F.conv2d(x, w, stride=2, padding=2)
+        gy = new(*y.shape)
+        xh, gh = x.detach().permute(0, 2, 3, 1).contiguous(), gy.permute(0, 2, 3, 1).contiguous()
+        jobs[name + ' wgrad_torch'] = lambda y=y, w=w, gy=gy: torch.autograd.grad(y, w, gy, retain_graph=True)
+        if transposed:
+            dw = torch.empty(cin, cout, 3, 3, device='cuda')
+            jobs[name + ' wgrad_hip'] = lambda xh=xh, gh=gh, dw=dw, cin=cin, cout=cout: \
+                ftl_train.wgrad(gh, xh, scratch, dw, cout, cout, 0, cin, 0, 2, 2)
+            packed = ftl_train.pack_dgrad_transpose(w.detach(), cout)
+            dx = torch.empty(N, hin, hin, cin, device='cuda')
+            jobs[name + ' dgrad_hip'] = lambda gh=gh, packed=packed, dx=dx, cin=cin, cout=cout: \
+                ftl.conv(gh, packed, None, dx, cout, 0, cin, 0, 2, 2, 1, False)
+        else:
+            dw = torch.empty(cout, cin, 3, 3, device='cuda')
+            jobs[name + ' wgrad_hip'] = lambda xh=xh, gh=gh, dw=dw, cin=cin, cout=cout: \
+                ftl_train.wgrad(xh, gh, scratch, dw, cin, cin, 0, cout, 0, 2, 2)
+            packed = ftl_train.pack_dgrad(w.detach(), cout)
+            dx = torch.empty(N, hin, hin, cin, device='cuda')
+            jobs[name + ' dgrad_hip'] = lambda gh=gh, packed=packed, dx=dx, cin=cin, cout=cout: \
+                ftl.conv(gh, packed, None, dx, cout, 0, cin, 0, 1, 0, 2, False)
+        jobs[name + ' dgrad_torch'] = lambda y=y, x=x, gy=gy: torch.autograd.grad(y, x, gy, retain_graph=True)
+    for key in ('encoder_head.0 dgrad_hip', 'encoder_head.0 dgrad_torch'):
+        del jobs[key]                                           # the features are frozen: no such pass in the step
+    _, _, N, h2, C2, _, _, _ = table['ftl_gather']
+    dcat, dsc = new(B, h2, h2, V * C2), new(N, h2, h2, C2)
+    o1, o2 = torch.empty(N, h2, h2, C2, device='cuda'), torch.empty(B, h2, h2, C2, device='cuda')
+
+    def transforms_hip():
+        ftl_train.gather_bwd_raw(dcat, coef_g, o1, B, V, C2, 0, C2, 0)
+        ftl_train.scatter_bwd_raw(dsc, coef_s, o2, B, V, C2, 0, 0)
+
+    At = lambda coef: coef[..., :9].reshape(B, V, 1, 3, 3).transpose(-1, -2)
+    tg, ts = dcat.permute(0, 3, 1, 2).reshape(B, V, C2, -1, 3), dsc.permute(0, 3, 1, 2).reshape(B, V, C2, -1, 3)
+    jobs['transforms bwd_hip'] = transforms_hip
+    jobs['transforms bwd_torch'] = lambda: (torch.matmul(tg, At(coef_g)), torch.matmul(ts, At(coef_s)).sum(1))
+    times = {}
+    for r in range(warmup + repeats):
+        for label, fn in jobs.items():
+            t = _time(fn, start, stop)
+            if r >= warmup:
+                times.setdefault(label, []).append(t)
+    out = {k: {'median_us': statistics.median(v), 'min_us': min(v), 'max_us': max(v)} for k, v in times.items()}
+    out['relative_difference_of_the_weight_gradients'] = diff
+    return out
+
+
 def _time(fn, start, stop):
     import torch
     start.record()
@@ -140,7 +287,7 @@ def torch_head(T, feat, coef_g, coef_s, B, V):
     return F.softmax(y.reshape(y.shape[0], y.shape[1], -1), 2).reshape(y.shape)
 
 
-def build_model(V, C=CHANNELS, K=JOINTS, seed=0):
+def build_model(V, C=CHANNELS, K=JOINTS, seed=0, trainable=False):
     """FTLMultiviewNet's HEAD with drawn weights and BatchNorm statistics, on the device, eval mode; no backbone is run"""
     import torch
     from config import cfg
@@ -153,7 +300,7 @@ def build_model(V, C=CHANNELS, K=JOINTS, seed=0):
     if C != CHANNELS:
         c.MODEL.EXTRA.STAGE4.NUM_CHANNELS = [C // 8, C // 8, C // 4, C // 2]
     torch.manual_seed(seed)
-    model = FTLMultiviewNet(c)
+    model = FTLMultiviewNet(c, trainable=True) if trainable else FTLMultiviewNet(c)
     with torch.no_grad():
         for name, m in model.named_modules():
             if name.startswith('backbone'):
@@ -236,13 +383,26 @@ def main(argv=None):
     ap.add_argument('--repeats', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--counts-only', action='store_true')
+    ap.add_argument('--train', action='store_true', help='the training step of the head instead of its inference')
     args = ap.parse_args(argv)
     if not args.counts_only:
         import torch
         if not torch.cuda.is_available():
             sys.exit('bench_ftl: no HIP device: the timings need one (--counts-only prints the cost model)')
     lines = []
-    for B in args.batches:
+    if args.train:
+        for B in args.batches:
+            row = {'B': B, 'V': args.views, 'train_counts': train_counts(B, args.views)}
+            if not args.counts_only:
+                row['times'] = t = measure_train(B, args.views, args.repeats, args.warmup)
+                for name in ('step',) + TRAIN_STAGES:
+                    h, o = t[name + '_hip'], t[name + '_torch']
+                    lines.append('--train B x V {} x {}  {:22s} hip {:.0f} ({:.0f} .. {:.0f}) us  torch {:.0f} ({:.0f} .. {:.0f}) '
+                                 'us  torch / hip {:.2f}'.format(B, args.views, name, h['median_us'], h['min_us'], h['max_us'],
+                                                                 o['median_us'], o['min_us'], o['max_us'],
+                                                                 o['median_us'] / h['median_us']))
+            print(json.dumps(row))
+    for B in ([] if args.train else args.batches):
         row = {'B': B, 'V': args.views, 'counts': counts(B, args.views)}
         if not args.counts_only:
             row['times'] = t = measure(B, args.views, args.repeats, args.warmup)

@@ -1407,6 +1407,45 @@ int hrnet_conv2d_3x3g(int dtype, const void* x, const void* w, const float* bias
                       int ldx, int x_off, int Cout, int ldy, int y_off, int Ho, int Wo, int stride, int pad_lo, int z,
                       int relu, hr_stream_t stream);
 
+/*
+ * Training of FTLMultiviewNet's head (csrc/ftl_train.hip): the backward of the two feature transforms and the weight
+ * gradient of hrnet_conv2d_3x3g at z = 1. f32 NHWC, channel slices as above, no atomics, a fixed summation order (stated
+ * at the top of the source file): two runs from the same state give equal bits. Anything an entry cannot serve is
+ * HR_E_BADARG before the first launch, and nothing is written. The cameras carry no gradient; coef is the forward's.
+ *
+ * ftl_gather_bwd: dx[b V + v] = dcat[b, slice v] A_bv^T per triplet and channel:
+ *   dx_i = fma(d2, A[i][2], fma(d1, A[i][1], d0 A[i][0])); the translation c plays no part.
+ *   dcat [B,H,W,ldd] read at channels [d_off + v slice, d_off + v slice + C) -> dx [B V,H,W,ldx] written at
+ *   [x_off, x_off + C), nothing else touched.
+ * ftl_scatter_bwd: df[b] = sum_v dy[b V + v] A_bv^T, the views added in order v = 0 .. V-1 inside one thread:
+ *   acc_i = 0; for v: acc_i = fma(d2, A[i][2], fma(d1, A[i][1], fma(d0, A[i][0], acc_i))).
+ *   dy [B V,H,W,ldy] read at [y_off, y_off + C) -> df [B,H,W,ldf] written once at [f_off, f_off + C).
+ * C, slice, every ld and offset are multiples of 4 and the maps 16-byte aligned, H W a multiple of 3, as in the forward.
+ *
+ * conv2d_3x3g_wgrad_scratch: pure host query: *bytes of scratch and *nsplit pixel-tile splits that conv2d_3x3g_wgrad uses
+ *   for N maps of Ho x Wo outputs and, if split_tiles != NULL, the 8 x 16 output-pixel tiles of one split. A function of
+ *   the shape alone (csrc/ftl_train_plan.h, on the rule of csrc/conv_kxk_split.h).
+ * conv2d_3x3g_wgrad: dw[co][ci][r][s] = sum_{n,ho,wo} dy[n,ho,wo,co] x[n, ho stride + r - pad_lo, wo stride + s - pad_lo, ci]
+ *   (x = 0 outside the map), stride 1 or 2, pad_lo 0 .. 2, in the Conv2d layout (Cout, Cin_real, 3, 3), overwritten.
+ *   x   [N,H,W,ldx] read at [x_off, x_off + Cin) (Cin, ldx, x_off multiples of 4, x 16-byte aligned); the first
+ *       Cin_real <= Cin channels have a gradient.
+ *   dy  [N,Ho,Wo,ldy] read at [y_off, y_off + Cout), any Cout >= 1, any offset. Ho and Wo must lie in the size range of
+ *       hrnet_conv2d_3x3g with z = 1 for H, W, stride and pad_lo.
+ *   scratch: the partial sums of the splits, at least *bytes of the query; a second launch adds them in split order.
+ *   The weight gradient of ConvTranspose2d(3, 2, 2, op) is this entry with the roles swapped: x := the layer's output
+ *   gradient, dy := the layer's input, stride 2, pad_lo 2, Ho := the input's height; the result (Cin_T, Cout_T, 3, 3) is
+ *   the ConvTranspose2d layout as it stands.
+ */
+int hrnet_ftl_gather_bwd(const float* dcat, const float* coef, float* dx, int B, int V, int H, int W, int C, int ldd,
+                         int d_off, int slice, int ldx, int x_off, hr_stream_t stream);
+int hrnet_ftl_scatter_bwd(const float* dy, const float* coef, float* df, int B, int V, int H, int W, int C, int ldy,
+                          int y_off, int ldf, int f_off, hr_stream_t stream);
+int hrnet_conv2d_3x3g_wgrad_scratch(int dtype, int N, int Ho, int Wo, int Cin, int Cout, HR_HOST long long* bytes,
+                                    HR_HOST int* nsplit, HR_HOST long long* split_tiles);
+int hrnet_conv2d_3x3g_wgrad(int dtype, const void* x, const void* dy, void* scratch, long long scratch_bytes, float* dw,
+                            int N, int H, int W, int Cin, int Cin_real, int ldx, int x_off, int Cout, int ldy, int y_off,
+                            int Ho, int Wo, int stride, int pad_lo, hr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
