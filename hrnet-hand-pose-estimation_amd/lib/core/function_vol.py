@@ -11,6 +11,10 @@ Running sums stay on the device and are read every PRINT_FREQ steps; the log lin
 reference's labels `Pose3DLoss` and `VolumetricCELoss` and the scalars `train_loss/pose3d_loss` and
 `train_loss/volumetric_ce_loss`; `validate` reports the mean 3-D end-point error in mm (`EPE3D`, `val/epe3d`).
 
+MHP_CPM_mv batches (MODEL.NAME vol_CPM) carry `centermaps`, which go to the model between the images and the
+projection matrices, and their own `heatmaps` target with k + 1 channels (the background first), which the heat-map term
+takes as it is; the loss composition is the same.
+
 Deviation from the reference, deliberate and the one core/function3D.py documents: A is the 3x3 frame-to-heat-map map
 obtained by inverting the reader's `hm_inverse` of each image. The reference's update_after_resize scales the
 intrinsics by 64/640 and 64/480, which does not invert the reader's crop.
@@ -24,7 +28,7 @@ import core.function3D as _f3d
 
 debug = False
 
-DATASETS = ('MHP_mv',)
+DATASETS = ('MHP_mv', 'MHP_CPM_mv')
 
 # (loss-dict key, LOSS flag, log label, LOSS factor)
 _LOSS_NAMES = (('pose3d_loss', 'WITH_POSE3D_LOSS', 'Pose3DLoss', 'POSE3D_LOSS_FACTOR'),
@@ -88,12 +92,16 @@ class AverageMeterVol(AverageMeter3D):
 
 
 def run_model(ret, model, device=None):
-    """one MHP_mv batch through the model -> its 7-tuple; differentiable when gradients are enabled"""
+    """one MHP_mv or MHP_CPM_mv batch through the model -> its 7-tuple; differentiable when gradients are enabled"""
     imgs = _to_device(ret['imgs'], device)                         # (B*V, 3, H, W), slot b * V + v
     extrinsic = ret['extrinsic_matrices']
     B, V = extrinsic.shape[:2]
     proj = heatmap_projections(ret['intrinsic_matrix'], extrinsic, ret['hm_inverse'])
-    return model(imgs.view(B, V, *imgs.shape[1:]), _to_device(proj.float(), device))
+    imgs = imgs.view(B, V, *imgs.shape[1:])
+    if 'centermaps' in ret:                                        # MHP_CPM_mv: the model on the CPM backbone
+        cm = _to_device(ret['centermaps'], device).float()
+        return model(imgs, cm.view(B, V, *cm.shape[1:]), _to_device(proj.float(), device))
+    return model(imgs, _to_device(proj.float(), device))
 
 
 def _forward_and_losses(config, ret, model, recorder, device):

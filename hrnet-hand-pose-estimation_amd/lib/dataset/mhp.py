@@ -441,7 +441,66 @@ class MHP_CPM_kpt(MHP):
                 'exception': np.array([self.exception])}
 
 
-READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq, 'MHP_mv': MHP_mv, 'MHP_CPM_kpt': MHP_CPM_kpt}
+class MHP_CPM_mv(MHP_mv):
+    """the reference's MHP_CPMMultiViewDataset (MHP_CPMMultiViewDataset.py:36-274), the reader of MODEL.NAME vol_CPM:
+    indexed like MHP_mv (frame i of the subset's directories, cameras `views`, slot b * V + v); per view what MHP_CPM_kpt
+    does, with these specifics: the whole frame resized to MODEL.IMAGE_SIZE, BGR, normalised as (v - 128) / 256; joints
+    projected without distortion (:97); `centermaps` (V, 1, H, W) the sigma = 3 Gaussian at the hand's centre; `heatmaps`
+    (V, 22, hm_h, hm_w) at MODEL.HEATMAP_SIZE, not stride 8 - channel 0 the background 1 - max, channel i + 1 the
+    sigma = DATASET.SIGMA Gaussian of joint i at int(coordinate) / (IMAGE_SIZE / HEATMAP_SIZE) (:211-226); `pose2d` in
+    heat-map pixels; no occlusion disc. It carries `pose3d`, `extrinsic_matrices` and `intrinsic_matrix` as MHP_mv does.
+    `hm_inverse` is the plain scale diag(640 / hm_w, 480 / hm_h): core.function_vol.heatmap_projections inverts it, which
+    is the reference's update_after_resize(K) [R|t] (lib/core/function3D.py:89-93) exactly. The reference applies no
+    random transform to this reader (TestResized(256) is the identity behind the resize), so is_train=True is allowed."""
+    name = 'MHP_CPM_mv'
+    bgr = True
+    stride = 8
+    mean = MHP_CPM_kpt.mean
+    std = MHP_CPM_kpt.std
+    resize = True
+
+    def __init__(self, cfg, subset, is_train=False, seed=0, views=VIEWS):
+        MHP_mv.__init__(self, cfg, subset, is_train, seed, views)
+        self.width, self.height = (int(v) for v in cfg.MODEL.IMAGE_SIZE)
+        if self.width % self.stride or self.height % self.stride:
+            raise ValueError('MHP_CPM_mv: MODEL.IMAGE_SIZE {}: multiples of {}'.format(list(cfg.MODEL.IMAGE_SIZE),
+                                                                                      self.stride))
+        self.hm_w, self.hm_h = (int(v) for v in cfg.MODEL.HEATMAP_SIZE)
+        self.sigma = cfg.DATASET.SIGMA
+
+    def __getitem__(self, key):
+        idx = key[0] if isinstance(key, tuple) else key
+        subdir, f = self.index[idx]
+        world = self.joints[(subdir, f)]
+        sx, sy = self.width / FRAME_W, self.height / FRAME_H
+        fx, fy = self.width / self.hm_w, self.height / self.hm_h
+        out = {k: [] for k in ('paths', 'pose2d', 'visibility', 'heatmaps', 'centermaps', 'exception',
+                               'extrinsic_matrices')}
+        for c in self.views:
+            out['paths'].append(os.path.join(frames_dir(self.data_dir), subdir, '{}_webcam_{}.jpg'.format(f, c)))
+            rvec, tvec = self.calib[(subdir, c)]
+            pose2d = project_points(world, rvec, tvec, INTRINSIC, np.zeros(5)) * np.array((sx, sy))
+            center, exception = cpm_center(pose2d, self.width, self.height)
+            heat = np.zeros((len(pose2d) + 1, self.hm_h, self.hm_w), dtype=np.float32)
+            for i, (x, y) in enumerate(pose2d):
+                heat[i + 1] = gaussian_map(self.hm_h, self.hm_w, int(x) / fx, int(y) / fy, self.sigma)
+            heat[0] = 1.0 - heat[1:].max(axis=0)
+            out['pose2d'].append(pose2d / np.array((fx, fy)))
+            out['visibility'].append(visibility(pose2d, self.width, self.height))
+            out['heatmaps'].append(heat)
+            out['centermaps'].append(gaussian_map(self.height, self.width, center[0], center[1], 3).astype(np.float32)[None])
+            out['exception'].append(exception)
+            out['extrinsic_matrices'].append(np.c_[rodrigues(rvec), tvec])
+        V = len(self.views)
+        out = {k: v if k == 'paths' else np.stack(v) for k, v in out.items()}
+        out.update(frames=1, views=V, pose3d=world, intrinsic_matrix=INTRINSIC,
+                   inverse=np.tile(np.array([[1 / sx, 0., 0.], [0., 1 / sy, 0.]]), (V, 1, 1)),
+                   hm_inverse=np.tile(np.array([[FRAME_W / self.hm_w, 0., 0.], [0., FRAME_H / self.hm_h, 0.]]), (V, 1, 1)))
+        return out
+
+
+READERS = {'MHP': MHP, 'MHP_kpt': MHP_kpt, 'MHP_seq': MHP_seq, 'MHP_mv': MHP_mv, 'MHP_CPM_kpt': MHP_CPM_kpt,
+           'MHP_CPM_mv': MHP_CPM_mv}
 CPM_KEYS = ('heatmaps', 'centermaps', 'exception')
 
 

@@ -163,6 +163,12 @@ class CPM(nn.Module):
             self._refuse(image, center_map, tape=True)
             return self._forward_train(image, center_map)
         self._refuse(image, center_map)
+        return tuple(self._infer(image, center_map)[0])
+
+    def _infer(self, image, center_map, keep=None, last_heat=True):
+        """the inference launches -> (the NCHW heat maps of stages 1 .. 6 (1 .. 5 without last_heat), the concatenated
+        map as stage 6 leaves it: its features, ITS heat maps, the centre map). keep: a dict that receives stage 6's four
+        ReLU outputs as m1 .. m4 (models.CPM_volumetric trains its last layers from them)"""
         with torch.no_grad():
             plan = self._packed()
             k1 = self.k + 1
@@ -181,13 +187,15 @@ class CPM(nn.Module):
             mid = self._trunk(plan, x, ('conv1_stage2', 'conv2_stage2', 'conv3_stage2'))
             for s in range(2, 7):
                 self._conv(plan, 'conv4_stage2' if s == 2 else 'conv1_stage{}'.format(s), mid, True, out=cat, y_off=0)
-                y = self._conv(plan, 'Mconv1_stage{}'.format(s), cat, True)
-                y = self._conv(plan, 'Mconv2_stage{}'.format(s), y, True)
-                y = self._conv(plan, 'Mconv3_stage{}'.format(s), y, True)
-                y = self._conv(plan, 'Mconv4_stage{}'.format(s), y, True)
+                y = cat
+                for i in (1, 2, 3, 4):
+                    y = self._conv(plan, 'Mconv{}_stage{}'.format(i, s), y, True)
+                    if keep is not None and s == 6:
+                        keep['m{}'.format(i)] = y
                 self._conv(plan, 'Mconv5_stage{}'.format(s), y, False, out=cat, y_off=FEAT)
-                outs.append(self._heat(cat))
-        return tuple(outs)
+                if s < 6 or last_heat:
+                    outs.append(self._heat(cat))
+        return outs, cat
 
     def _heat(self, cat):
         """the k + 1 heat-map channels of the concatenated map as an NCHW tensor"""

@@ -20,7 +20,8 @@ lifting, DLT or --triangulation ransac, is the same.
 
 The reference lifts pose_hrnet predictions with DLT_sii_pytorch (lib/utils/misc.py:64-97), two shifted inverse
 iterations from a torch.rand start; this tool computes the vector they converge to (see utils/multiview.py).
-The models alg, ransac, vol, vol_CPM and FTL are not built: they are refused with a ValueError.
+The models alg, ransac, vol, vol_CPM and FTL are not built in this tool: they are refused with a ValueError (vol and
+vol_CPM are evaluated by tools/evaluate_vol.py, FTL by tools/evaluate_ftl.py).
 
 --triangulation ransac lifts with the reference's RANSAC over the views instead (lib/utils/misc.py:178-240, called by
 RANSACTriangulationNet.forward, lib/models/triangulation.py:72-118), as a lifting method for the same two models: ONE
@@ -110,6 +111,8 @@ def parse_views(text):
 def build_model(name):
     if name in NOT_BUILT:
         hint = ' (RANSAC is a lifting method here: --triangulation ransac)' if name == 'ransac' else ''
+        if name in ('vol', 'vol_CPM'):
+            hint = ' (the volumetric models are evaluated by tools/evaluate_vol.py)'
         raise ValueError('MODEL.NAME {!r} is not built in this project: tools/evaluate_3D.py evaluates {}{}'.format(
             name, ' / '.join(MODELS), hint))
     if name not in MODELS:

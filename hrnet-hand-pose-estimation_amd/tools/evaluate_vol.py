@@ -12,6 +12,8 @@ model, then core/evaluate3d.py's accumulators fed with `vol_keypoints_3d` and th
 mse2d_each_joint.txt, mse3d_each_joint.txt, PCK2d.txt and PCK3d.txt to <OUTPUT_DIR>/eval3D_results_<EXP_NAME>/.
 Refusals are tools/train_vol.py's that apply: a MODEL.NAME other than vol and what models/triangulation.py refuses;
 --model_path is required and must exist (the tool never evaluates random weights).
+MODEL.NAME vol_CPM (experiments/MHP/MHP_VolTriangulation_CPM_v1.yaml) is evaluated the same way: the model is
+VolumetricTriangulationNet_CPM, the reader MHP_CPM_mv, the refusals check_vol_cpm_config's.
 """
 import argparse
 import os
@@ -28,9 +30,13 @@ from core.evaluate3d import Eval3DAccumulator, auc
 from core.function_vol import run_model
 from dataset import mhp
 from evaluate_3D import parse_views
-from models.triangulation import VolumetricTriangulationNet, check_vol_config
+from models.triangulation import (VolumetricTriangulationNet, VolumetricTriangulationNet_CPM, check_vol_config,
+                                  check_vol_cpm_config)
 
 MODEL_NAME = 'vol'
+# MODEL.NAME -> (the model, what it refuses of a config, its multi-view reader)
+MODELS = {'vol': (VolumetricTriangulationNet, check_vol_config, 'MHP_mv'),
+          'vol_CPM': (VolumetricTriangulationNet_CPM, check_vol_cpm_config, 'MHP_CPM_mv')}
 
 
 def parse_args(argv=None):
@@ -46,11 +52,11 @@ def parse_args(argv=None):
 
 
 def check_config(config):
-    if config.MODEL.NAME != MODEL_NAME:
+    if config.MODEL.NAME not in MODELS:
         raise ValueError('MODEL.NAME {!r}: tools/evaluate_vol.py evaluates the volumetric triangulation model, '
-                         'MODEL.NAME {!r} (tools/evaluate_3D.py evaluates the 2-D models by triangulation)'.format(
-                             config.MODEL.NAME, MODEL_NAME))
-    check_vol_config(config)
+                         'MODEL.NAME {!r} (or vol_CPM, the same on the CPM backbone; tools/evaluate_3D.py evaluates the '
+                         '2-D models by triangulation)'.format(config.MODEL.NAME, MODEL_NAME))
+    MODELS[config.MODEL.NAME][1](config)
 
 
 def main(argv=None):
@@ -68,13 +74,14 @@ def main(argv=None):
                  '(DATA_DIR/MHP/annotated_frames)'.format(frames))
     device = torch.device('cuda', max(args.gpu, 0))
     torch.cuda.set_device(device)
-    model = VolumetricTriangulationNet(cfg, is_train=False)
+    model_class, _check, reader = MODELS[cfg.MODEL.NAME]
+    model = model_class(cfg, is_train=False)
     load_checkpoint_state(model, args.model_path)          # strict, `module.` stripped
     model = model.to(device).eval()
     c = cfg.clone()
     c.defrost()
     c.TEST.IMAGES_PER_GPU = args.batch_size
-    loader = mhp.make_loader(c, 'MHP_mv', cfg.DATASET.TEST_SET, False, max_batches=args.num_batches, views=views)
+    loader = mhp.make_loader(c, reader, cfg.DATASET.TEST_SET, False, max_batches=args.num_batches, views=views)
     K, V = cfg.MODEL.NUM_JOINTS, len(views)
     acc = Eval3DAccumulator(K, cfg.MODEL.HEATMAP_SIZE[0])
     timed, t_total = 0, 0.0

@@ -22,6 +22,12 @@ Refused before any device work (check_config): a MODEL.NAME other than vol; what
 aggregation, a VOLUME_SIZE that is no multiple of 32, another BACKBONE_NAME, MODEL.ALG_CONFIDENCES); a dataset other
 than MHP_mv; LOSS.WITH_POSE3D_LOSS false and the loss terms this loop does not evaluate; a missing
 <DATA_DIR>/MHP/annotated_frames; WORLD_SIZE > 1 (data-parallel training of this model is not built).
+
+MODEL.NAME vol_CPM (experiments/MHP/MHP_VolTriangulation_CPM_v1.yaml) is the same model on the CPM backbone
+(VolumetricTriangulationNet_CPM on CPM_volumetric), trained on the reader MHP_CPM_mv, whose batches carry the centre
+maps and the k + 1 channel heat-map targets. The three Adam groups are the same; `backbone` then means
+Mconv3/4/5_stage6, the only layers of CPM_volumetric that train. It refuses what check_vol_cpm_config refuses
+(MODEL.VOL_CONFIDENCES false among it) and any reader but MHP_CPM_mv.
 """
 import os
 import pprint
@@ -30,14 +36,18 @@ import _init_paths  # noqa: F401
 import torch
 
 from config import cfg, update_config
-from core.function_vol import DATASETS, train, validate
+from core.function_vol import train, validate
 from core.loss import HeatmapLoss, Joints3DMSELoss, JointsMSELoss, VolumetricCELoss
 from dataset import mhp
-from models.triangulation import VolumetricTriangulationNet, check_vol_config
+from models.triangulation import (VolumetricTriangulationNet, VolumetricTriangulationNet_CPM, check_vol_config,
+                                  check_vol_cpm_config)
 from train3D import parse_args, parse_views          # one set of flags and one rule for --views in the 3-D tools
 from utils.utils import create_logger, save_checkpoint
 
 MODEL_NAME = 'vol'
+# MODEL.NAME -> (the model, what it refuses of a config, the multi-view reader it trains and validates on)
+MODELS = {'vol': (VolumetricTriangulationNet, check_vol_config, 'MHP_mv'),
+          'vol_CPM': (VolumetricTriangulationNet_CPM, check_vol_cpm_config, 'MHP_CPM_mv')}
 UNUSED_TERMS = ('WITH_BONE_LOSS', 'WITH_JOINTANGLE_LOSS', 'WITH_TIME_CONSISTENCY_LOSS', 'WITH_KCS_LOSS',
                 'WITH_KCS_TC_LOSS')
 GROUPS = (('backbone', 'LR'), ('process_features', 'PROCESS_FEATURE_LR'), ('volume_net', 'VOLUME_NET_LR'))
@@ -45,16 +55,17 @@ GROUPS = (('backbone', 'LR'), ('process_features', 'PROCESS_FEATURE_LR'), ('volu
 
 def check_config(config, world=1):
     """everything this tool refuses, checked before any device work; raises ValueError or NotImplementedError"""
-    if config.MODEL.NAME != MODEL_NAME:
+    if config.MODEL.NAME not in MODELS:
         raise ValueError('MODEL.NAME {!r}: tools/train_vol.py trains the volumetric triangulation model, MODEL.NAME '
-                         '{!r} (tools/train3D.py trains pose_hrnet_softmax on the 3-D loss)'.format(config.MODEL.NAME,
-                                                                                                   MODEL_NAME))
-    check_vol_config(config)
+                         '{!r} (or vol_CPM, the same on the CPM backbone; tools/train3D.py trains pose_hrnet_softmax on '
+                         'the 3-D loss)'.format(config.MODEL.NAME, MODEL_NAME))
+    _model, check, reader = MODELS[config.MODEL.NAME]
+    check(config)
     for key, names in (('DATASET.DATASET', config.DATASET.DATASET), ('DATASET.TEST_DATASET',
                                                                      config.DATASET.TEST_DATASET)):
-        if not names or any(n not in DATASETS for n in names):
+        if not names or any(n != reader for n in names):
             raise ValueError('{} {}: the volumetric model trains and validates on the multi-view reader {}'.format(
-                key, list(names), list(DATASETS)))
+                key, list(names), [reader]))
     if not config.LOSS.WITH_POSE3D_LOSS:
         raise ValueError('LOSS.WITH_POSE3D_LOSS false: tools/train_vol.py trains the 3-D loss of the volumetric model')
     on = [k for k in UNUSED_TERMS if getattr(config.LOSS, k)]
@@ -116,7 +127,7 @@ def main(argv=None):
     c.defrost()
     c.MODEL.BACKBONE_MODEL_PATH = start
     c.freeze()
-    model = VolumetricTriangulationNet(c, is_train=True)
+    model = MODELS[cfg.MODEL.NAME][0](c, is_train=True)
     best_perf, begin_epoch = float('inf'), cfg.TRAIN.BEGIN_EPOCH
     ckpt_file = os.path.join(final_output_dir, 'checkpoint.pth.tar')
     ckpt = None
@@ -137,7 +148,8 @@ def main(argv=None):
         writer_dict['train_global_steps'] = ckpt.get('train_global_steps', 0)
         writer_dict['valid_global_steps'] = ckpt.get('valid_global_steps', 0)
 
-    heatmaps = bool(cfg.LOSS.WITH_HEATMAP_LOSS)
+    # MHP_CPM_mv carries its own heat maps (k + 1 channels, the background first): the loader generates none
+    heatmaps = bool(cfg.LOSS.WITH_HEATMAP_LOSS) and cfg.MODEL.NAME == MODEL_NAME
     train_loader = {n: mhp.make_loader(cfg, n, cfg.DATASET.TRAIN_SET, True, 0, 1, False, args.batches_per_epoch,
                                        heatmaps, views=views) for n in cfg.DATASET.DATASET}
     valid_loader = {n: mhp.make_loader(cfg, n, cfg.DATASET.TEST_SET, False, heatmaps=heatmaps, views=views)

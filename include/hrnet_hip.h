@@ -1446,6 +1446,30 @@ int hrnet_conv2d_3x3g_wgrad(int dtype, const void* x, const void* dy, void* scra
                             int N, int H, int W, int Cin, int Cin_real, int ldx, int x_off, int Cout, int ldy, int y_off,
                             int Ho, int Wo, int stride, int pad_lo, hr_stream_t stream);
 
+/*
+ * The bridge from the CPM backbone's f32 NHWC maps to the volumetric half's f32 NCHW maps (csrc/upsample_slice.hip):
+ * a channel slice of an NHWC map, resampled bilinearly with align_corners, written as NCHW.
+ *
+ * upsample_slice_nchw: dst [N,C,H,W] = F.interpolate(src[..., c0 : c0 + C] as NCHW, size = (H, W), mode = 'bilinear',
+ *   align_corners = True), src [N,h,w,Cp]. Positions as torch computes them: scale = float(in - 1) / float(out - 1) (0 when
+ *   out == 1), pos = scale * index in f32, lower = int(pos), upper = lower + (lower < in - 1), lambda = pos - lower; the
+ *   value is (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11). Any h, w, H, W >= 1 (down-sampling and equal
+ *   sizes included), any 0 <= c0, C >= 1, c0 + C <= Cp; no alignment beyond that of a float.
+ * upsample_slice_nchw_bwd: the exact transpose in gather form: every element of the slice of dsrc [N,h,w,Cp] is the sum,
+ *   Y ascending then X ascending, of weight(Y, y) weight(X, x) ddst[n][c][Y][X] over its footprint (the outputs that name
+ *   it as a neighbour, found from the same f32 positions). One thread owns one element: no atomics, equal bits on every
+ *   run. accumulate 0 writes the slice (zero where nothing reads a source pixel), 1 adds onto what is there; channels
+ *   outside [c0, c0 + C) keep their bits in both modes.
+ * upsample_slice_nchw_supported: 1 when [c0, c0 + C) is a slice of a row of Cp channels, else 0.
+ * Anything an entry cannot serve (a null or aliased pointer, an empty axis, a map of 2^31 pixels, a slice outside its
+ * row) is HR_E_BADARG before the launch, and nothing is written.
+ */
+int hrnet_upsample_slice_nchw(const float* src, float* dst, int N, int h, int w, int Cp, int c0, int C,
+                              int H, int W, hr_stream_t stream);
+int hrnet_upsample_slice_nchw_bwd(const float* ddst, float* dsrc, int N, int h, int w, int Cp, int c0, int C,
+                                  int H, int W, int accumulate, hr_stream_t stream);
+hr_value_t hrnet_upsample_slice_nchw_supported(int Cp, int c0, int C);
+
 #ifdef __cplusplus
 }
 #endif
