@@ -10,8 +10,8 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(CSRC, 'libhrnet_hip.so')
-SOURCES = ['api.hip', 'conv.hip', 'conv_bs.hip', 'conv_fwd.hip', 'conv_dg.hip', 'conv_fwdb.hip', 'conv_fwds.hip', 'conv_ring.hip', 'wgrad.hip', 'bwd_fused.hip', 'bwd_pw.hip', 'gemm_pw.hip', 'head_mix.hip', 'eltwise.hip', 'loss.hip', 'dcn.hip', 'preprocess.hip', 'triangulate.hip', 'volumetric.hip', 'conv3d.hip', 'conv3d_train.hip', 'pointwise.hip', 'view_fusion.hip', 'transformer.hip', 'swin.hip', 'nmf.hip', 'burger_train.hip', 'conv_kxk.hip', 'conv_kxk_train.hip', 'ftl.hip', 'ftl_train.hip', 'upsample_slice.hip']
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'conv_body.h'), os.path.join(CSRC, 'conv_ring.h'), os.path.join(CSRC, 'conv_kxk_body.h'), os.path.join(CSRC, 'conv_kxk_split.h'), os.path.join(CSRC, 'ftl_train_plan.h'), os.path.join(REPO, 'include', 'hrnet_hip.h')]
+SOURCES = ['api.hip', 'conv.hip', 'conv_bs.hip', 'conv_fwd.hip', 'conv_dg.hip', 'conv_fwdb.hip', 'conv_fwds.hip', 'conv_ring.hip', 'wgrad.hip', 'bwd_fused.hip', 'bwd_pw.hip', 'gemm_pw.hip', 'head_mix.hip', 'eltwise.hip', 'loss.hip', 'dcn.hip', 'preprocess.hip', 'triangulate.hip', 'volumetric.hip', 'conv3d.hip', 'conv3d_train.hip', 'pointwise.hip', 'view_fusion.hip', 'transformer.hip', 'swin.hip', 'nmf.hip', 'burger_train.hip', 'conv_kxk.hip', 'conv_kxk_train.hip', 'ftl.hip', 'ftl_train.hip', 'upsample_slice.hip', 'predrnn.hip']
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'conv_body.h'), os.path.join(CSRC, 'conv_ring.h'), os.path.join(CSRC, 'conv_kxk_body.h'), os.path.join(CSRC, 'conv_kxk_split.h'), os.path.join(CSRC, 'ftl_train_plan.h'), os.path.join(CSRC, 'predrnn_plan.h'), os.path.join(REPO, 'include', 'hrnet_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc',
          '-I', os.path.join(REPO, 'include'), '-I', CSRC, '-Wno-unused-result']

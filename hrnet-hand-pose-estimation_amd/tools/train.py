@@ -24,7 +24,7 @@ from config import cfg, update_config
 from core.function import train, validate
 from core.loss import BoneLengthLoss, HeatmapLoss, JointAngleLoss, JointsMSELoss
 from dataset.build import make_dataloader
-from models import CPM, pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, swin_transformer  # noqa: F401  (dispatched by name below)
+from models import CPM, pose_hrnet, pose_hrnet_PoseAggr, pose_hrnet_hamburger, pose_hrnet_softmax, pose_hrnet_transformer, predrnn, swin_transformer  # noqa: F401  (dispatched by name below)
 from utils.utils import create_logger, get_optimizer, save_checkpoint
 
 
@@ -72,6 +72,10 @@ def check_config(cfg):
         raise ValueError('MODEL.NAME CPM: {} (no backward of the K x K convolution and the pools, no six-stage heat-map '
                          'loss, no training transforms in MHP_CPM_kpt); evaluation works: tools/evaluate_2D.py runs '
                          'it'.format(CPM.NOT_BUILT))
+    if cfg.MODEL.NAME == 'predrnn':
+        raise ValueError('MODEL.NAME predrnn: {} (no backward through the L x layers spatio-temporal LSTM cells, no 3-D '
+                         'pose loss on frame windows); inference works: tools/evaluate_predrnn.py runs it'.format(
+                             predrnn.NOT_BUILT))
 
 
 def main():

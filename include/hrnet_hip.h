@@ -1470,6 +1470,45 @@ int hrnet_upsample_slice_nchw_bwd(const float* ddst, float* dsrc, int N, int h, 
                                   int H, int W, int accumulate, hr_stream_t stream);
 hr_value_t hrnet_upsample_slice_nchw_supported(int Cp, int c0, int C);
 
+/*
+ * The spatio-temporal LSTM cell of PredRNN between its convolutions (lib/models/predrnn.py:33-58 of the reference) and
+ * the MaxPool2d(2, 2) of the model's ResNet tail (csrc/predrnn.hip). f32 NHWC, inference, no atomics, a fixed summation
+ * order (stated at the top of the source file): two runs give equal bits. Anything an entry cannot serve is HR_E_BADARG
+ * before the first launch, and nothing is written. Every map is 16-byte aligned.
+ *
+ * sample_stats: nn.LayerNorm([C, W, W])'s statistics: for up to three dense maps x_m [B, n_m] (n_m = H W C_m elements per
+ *   sample, a multiple of 4; n_m = 0 and x_m = NULL: map absent, the maps present first) stats[(m B + b) 2] = mean and
+ *   [.. + 1] = rstd = 1 / sqrt(var + eps) of sample b of map m, var the biased variance. All sums in double on data shifted
+ *   by the sample's first element, rounded to float once. scratch: at least *bytes of sample_stats_scratch (a pure host
+ *   query, a function of the shape alone: csrc/predrnn_plan.h), 8-byte aligned.
+ * stlstm_gates: xc [B,H,W,7 nh] (slices i f g i' f' g' o), hc [B,H,W,4 nh] (i f g o), mc [B,H,W,3 nh] (i f g): the raw
+ *   outputs of conv_x, conv_h, conv_m; stats [3][B][2] of sample_stats over them in that order; wx, bx [H,W,7 nh], wh, bh
+ *   [H,W,4 nh], wm, bm [H,W,3 nh]: the LayerNorm weights and biases repacked from (C, H, W). With
+ *   LN(v) = fma((v - mean) rstd, w, b):
+ *     c_new = sigmoid(i_x + i_h) tanh(g_x + g_h) + sigmoid(f_x + f_h + 1) c_t     -> mem channels [0, nh)
+ *     m_new = sigmoid(i'_x + i_m) tanh(g'_x + g_m) + sigmoid(f'_x + f_m + 1) m_t  -> mem channels [nh, 2 nh)
+ *     o_pre = o_x + o_h                                                           -> o_pre [B,H,W,nh]
+ *   c_t [B,H,W,ldc] read at [c_off, c_off + nh), m_t [B,H,W,ldmt] at [m_off, m_off + nh), mem [B,H,W,ldmem], nothing outside
+ *   its first 2 nh channels written; nh, every ld and offset multiples of 4. c_t may be mem's own slice [0, nh) and m_t its
+ *   slice [nh, 2 nh) (same pointer and row length): every thread reads its own elements before it writes them. Any other
+ *   overlap of an input with an output is refused.
+ * stlstm_out: h_new [B,H,W,nh] = sigmoid(o_pre + LN(oc)) tanh(last): oc the raw conv_o output with its stats [B][2] and
+ *   affine wo, bo [H,W,nh]; last the conv_last output.
+ * maxpool2d_2x2: nn.MaxPool2d(2, 2): x [N,H,W,ldx] channels [x_off, x_off + C) -> y [N,H/2,W/2,ldy] channels
+ *   [y_off, y_off + C); even H and W; C, every ld and offset multiples of 4; a NaN wins.
+ */
+int hrnet_sample_stats_scratch(int B, long long n0, long long n1, long long n2, HR_HOST long long* bytes);
+int hrnet_sample_stats(const float* x0, const float* x1, const float* x2, long long n0, long long n1, long long n2, int B,
+                       double eps, void* scratch, long long scratch_bytes, float* stats, hr_stream_t stream);
+int hrnet_stlstm_gates(const float* xc, const float* hc, const float* mc, const float* stats, const float* wx,
+                       const float* bx, const float* wh, const float* bh, const float* wm, const float* bm,
+                       const float* c_t, int ldc, int c_off, const float* m_t, int ldmt, int m_off, float* mem, int ldmem,
+                       float* o_pre, int B, int H, int W, int nh, hr_stream_t stream);
+int hrnet_stlstm_out(const float* oc, const float* stats, const float* wo, const float* bo, const float* o_pre,
+                     const float* last, float* h_new, int B, int H, int W, int nh, hr_stream_t stream);
+int hrnet_maxpool2d_2x2(const float* x, float* y, int N, int H, int W, int C, int ldx, int x_off, int ldy, int y_off,
+                        hr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
